@@ -29,6 +29,12 @@ Roofline: the dominant kernel's algorithmic FLOPs per launch / its average HIP-e
 time inside the timed region.  traffic: HBM bytes per launch of that kernel from two
 rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over a short child run of this same
 script, config, E and library (N = 1 only; null when rocprofv3 is absent or --no-pmc).
+
+A plain run sets up, warms up, times the steps and prints the result line (the roofline's achieved / frac
+come from the HIP events inside the timed steps).  --full adds the legs that take runs of their own: the CPU
+baseline, the rocprofv3 kernel-trace and --pmc child runs (frac_rocprof, traffic) and hbm_kernels.
+--dump-outputs DIR writes what the last timed step left (parameters, gradient buffers, losses, the envs'
+observations) as DIR/<name>.npy; seeds are fixed, so equal arguments give equal inputs from run to run.
 """
 import argparse
 import hashlib
@@ -141,7 +147,19 @@ def parse():
                     help="step the envs on the host CPU (HostSynthEnv: vectorised numpy SynthEnv behind pinned "
                          "staging + side-stream copies, the update overlapping the host step): the PCIe-inclusive "
                          "host-simulator rate, not the metric")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the rocprofv3 "
+                         "kernel-trace and --pmc child runs (roofline frac_rocprof, traffic) and the HBM-bound kernels' "
+                         "launches after the timed region (hbm_kernels); --no-cpu-baseline / --no-pmc / --no-rocprof "
+                         "take single legs out again.  Without it the run sets up, warms up, times the steps and "
+                         "prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path left in its last step (every network's "
+                         "parameters and gradient buffers, the losses, the envs' observations) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB in all")
     a = ap.parse_args()
+    if not a.full:
+        a.no_cpu_baseline = a.no_pmc = a.no_rocprof = True
     st, wu = DEFAULT_STEPS.get(a.config, (200, 10))
     a.steps = st if a.steps is None else a.steps
     a.warmup = wu if a.warmup is None else a.warmup
@@ -440,6 +458,42 @@ def hbm_kernels(ag, cfg, B, E):
     return out
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_BYTES = 64 << 20
+NET_NAMES = ["actor", "critic_1", "critic_2", "critic_1_targ", "critic_2_targ", "acm", "actor_targ"]  # SPP_NET_*
+
+
+def dump_outputs(path, arrays, prefix=""):
+    """Write {name: tensor | array | float} as ``path/<prefix><name>.npy``: float64 stays float64, every other
+    dtype becomes float32.  The files together hold at most DUMP_BYTES: an array over its equal share of that is
+    cut to a fixed sample of its flattened elements (sorted indices from RandomState(0), the same in every run)."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        v = np.asarray(v)
+        out[name] = np.ascontiguousarray(v if v.dtype == np.float64 else v.astype(np.float32))
+    share = DUMP_BYTES // max(len(out), 1)
+    for name, v in out.items():
+        if v.nbytes > share:
+            keep = np.sort(np.random.RandomState(0).choice(v.size, share // v.itemsize, replace=False))
+            v = v.reshape(-1)[keep]
+        np.save(os.path.join(path, "%s%s.npy" % (prefix, name)), v)
+
+
+def agent_outputs(params, grads, losses, obs):
+    """The arrays a caller of the timed step holds after it: parameters and gradient buffers by network (dicts
+    keyed by SPP_NET_*), the loss scalars (float64) and the envs' current observations."""
+    out = {"params_" + NET_NAMES[k]: p for k, p in params.items()}
+    out.update({"grads_" + NET_NAMES[k]: g for k, g in grads.items()})
+    out.update({"loss_" + k: np.array([v], dtype=np.float64) for k, v in losses.items()
+                if isinstance(v, (int, float))})
+    if obs is not None:
+        out["obs"] = obs
+    return out
+
+
 # ------------------------------------------------------------------ PPO_AcM (configs[3])
 def bench_ppo(args, world, rank, dev, comm=None):
     """configs[3]: SPP-PPO HalfCheetah-v2, 16384 envs over 8 GPUs = 2048 per GPU (train/spp_ppo_hcheetah.py
@@ -523,6 +577,13 @@ def bench_ppo(args, world, rank, dev, comm=None):
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        from spprl import _lib
+
+        dump_outputs(args.dump_outputs, agent_outputs(
+            {_lib.SPP_NET_ACTOR: ag.nets.params[0], _lib.SPP_NET_CRITIC1: ag.nets.params[1],
+             _lib.SPP_NET_ACM: ag.acm.params[_lib.SPP_NET_ACM]},
+            {}, ag.loss, ag._obs))  # (nets.grads are exchange buffers of the data-parallel path: zeros on one GPU)
     value = wj * N * args.steps / elapsed
     mac = flops.onpolicy_macs(ob, ob, ac)
     # algorithmic work of the timed iterations: 100 full-batch critic steps on N samples, the PPO
@@ -901,6 +962,9 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, agent_outputs(ag.params, ag.grads, losses, ag._obs),
+                     "replica%s_" % os.environ.get("SPP_REPLICA_INDEX", "0") if args.replica_worker else "")
 
     if cfg["algo"] == "ddpg":
         mac = flops.ddpg_macs(ob, ac)
@@ -968,7 +1032,7 @@ def main():
         allc = [torch.empty_like(chk) for _ in range(world)]
         dist.all_gather(allc, chk)
         result["replicas_identical"] = bool(all(torch.equal(allc[0], c) for c in allc))
-    if world == 1 and not args.replica_worker:
+    if world == 1 and not args.replica_worker and args.full:
         result["hbm_kernels"] = hbm_kernels(ag, cfg, B, E)
     if rank == 0 and world == 1 and not args.no_rocprof:
         kt_ms, kt_src = rocprof_kernel_ms(args, E, cap, kname)

@@ -105,10 +105,28 @@ from rltoolkit.buffer import BufferAcMOffPolicy, Memory  # noqa: E402
 torch.set_num_threads(1)
 
 
+PART_BYTES = 900_000  # uncompressed bytes per file: every committed fixture file stays under 1 MiB
+
+
+def split_parts(arrays):
+    """Arrays in their order, cut into parts of at most PART_BYTES (golden_cases.load merges them again)."""
+    parts, size = [{}], 0
+    for k, a in arrays.items():
+        a = np.asarray(a)
+        if parts[-1] and size + a.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += a.nbytes
+    return parts
+
+
 def save(name, **arrays):
-    path = os.path.join(HERE, name)
-    np.savez_compressed(path, **arrays)
-    print("wrote", path, sum(a.size for a in arrays.values()), "values")
+    """name.npz, then name.part1.npz, name.part2.npz, ... where one file would pass PART_BYTES."""
+    for i, part in enumerate(split_parts(arrays)):
+        path = os.path.join(HERE, name if i == 0 else name[:-4] + ".part%d.npz" % i)
+        np.savez_compressed(path, **part)
+        print("wrote", path, sum(a.size for a in part.values()), "values")
 
 
 # ---------------------------------------------------------------- MT19937 randint

@@ -20,7 +20,16 @@ SAC_CASES = {
 
 
 def load(name):
-    return dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    """name.npz and its continuation files name.part1.npz, name.part2.npz, ... (make_golden.save keeps every
+    file under the size limit for committed files) as one dict."""
+    fx = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    i = 1
+    while os.path.exists(os.path.join(GOLDEN, "%s.part%d.npz" % (name, i))):
+        part = dict(np.load(os.path.join(GOLDEN, "%s.part%d.npz" % (name, i))))
+        assert not set(part) & set(fx), (name, i)
+        fx.update(part)
+        i += 1
+    return fx
 
 
 def make_batch(rng, B, ob, aout, ac, done_p=0.15):
