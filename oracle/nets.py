@@ -118,9 +118,9 @@ def flatten(p):
     return torch.cat([v.detach().reshape(-1) for v in p.values()])
 
 
-def unflatten(flat, layout, requires_grad=False):
+def unflatten(flat, layout, requires_grad=False, dtype=torch.float32):
     out, o = {}, 0
-    flat = torch.as_tensor(flat, dtype=torch.float32)
+    flat = torch.as_tensor(flat, dtype=dtype)
     for name, shape in layout:
         n = int(np.prod(shape))
         out[name] = flat[o:o + n].reshape(shape).clone().requires_grad_(requires_grad)

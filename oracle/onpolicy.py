@@ -88,9 +88,13 @@ def critic_steps(flat, ob, x, q, lr, nsteps, dtype=torch.float32):
     return p.numpy(), losses
 
 
-def actor_step(flat, ob, aout, lim, x, act, lp_old, adv, eps_clip=0.2, entropy_coef=0.0, next_obs=None):
+def actor_step(flat, ob, aout, lim, x, act, lp_old, adv, eps_clip=0.2, entropy_coef=0.0, next_obs=None,
+               dtype=torch.float32):
     """Returns ({actor, kl, entropy, dist}, grad) of clip_loss - entropy_coef * entropy."""
-    p = _params(flat, actor_layout(ob, aout))
+    p = _params(flat, actor_layout(ob, aout), dtype)
+    x, act, lp_old, adv, lim = (torch.as_tensor(np.asarray(t)).to(dtype) for t in (x, act, lp_old, adv, lim))
+    if next_obs is not None:
+        next_obs = torch.as_tensor(np.asarray(next_obs)).to(dtype)
     dist = actor_dist(p, torch.as_tensor(x), torch.as_tensor(lim))
     lp_new = dist.log_prob(torch.as_tensor(act))
     ratio = torch.exp(lp_new - torch.as_tensor(lp_old))
