@@ -15,20 +15,25 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import bf16 as bf
+
 LOG2 = float(np.log(2))
 LOG_SQRT_2PI = math.log(math.sqrt(2 * math.pi))
 
 
-def lin(x, p, name):
-    return F.linear(x, p[name + ".weight"], p[name + ".bias"])
+def lin(x, p, name, mode=None):
+    """mode: an oracle.bf16.Mode, the operand roundings of the bf16 kernel sets (None: F.linear)."""
+    return bf.linear(x, p[name + ".weight"], p[name + ".bias"], mode)
 
 
-def sac_actor(p, x, lim, eps=None):
-    """Returns (action, logprob, u).  eps=None -> deterministic (action = tanh(mu)*lim)."""
-    h = torch.relu(lin(x, p, "fc1"))
-    h = torch.relu(lin(h, p, "fc2"))
-    mu = lin(h, p, "fc_prob")
-    ls = torch.clamp(lin(h, p, "fc_scale"), -20, 2)
+def sac_actor(p, x, lim, eps=None, bf16=False):
+    """Returns (action, logprob, u).  eps=None -> deterministic (action = tanh(mu)*lim).
+    bf16: the layers round their operands as the bf16 kernel sets do (oracle/bf16.py)."""
+    hid, head = (bf.HIDDEN, bf.HEAD) if bf16 else (None, None)
+    h = torch.relu(lin(x, p, "fc1", hid))
+    h = torch.relu(lin(h, p, "fc2", hid))
+    mu = lin(h, p, "fc_prob", head)
+    ls = torch.clamp(lin(h, p, "fc_scale", head), -20, 2)
     scale = torch.exp(ls)
     u = mu if eps is None else mu + eps * scale
     var = scale ** 2
@@ -38,11 +43,12 @@ def sac_actor(p, x, lim, eps=None):
     return torch.tanh(u) * lim, lp, u
 
 
-def sac_critic(p, obs, ac):
+def sac_critic(p, obs, ac, bf16=False):
+    hid, fc3 = (bf.HIDDEN, bf.CRITIC_FC3) if bf16 else (None, None)
     x = torch.cat((obs, ac), dim=-1)
-    x = torch.relu(lin(x, p, "fc1"))
-    x = torch.relu(lin(x, p, "fc2"))
-    return torch.squeeze(lin(x, p, "fc3"), -1)
+    x = torch.relu(lin(x, p, "fc1", hid))
+    x = torch.relu(lin(x, p, "fc2", hid))
+    return torch.squeeze(lin(x, p, "fc3", fc3), -1)
 
 
 ddpg_critic = sac_critic
@@ -54,10 +60,11 @@ def ddpg_actor(p, x, lim):
     return torch.tanh(lin(h, p, "fc3")) * lim
 
 
-def acm(p, x, lim):
-    x = torch.tanh(lin(x, p, "fc1"))
-    x = torch.tanh(lin(x, p, "fc2"))
-    return torch.tanh(lin(x, p, "fc3")) * lim
+def acm(p, x, lim, bf16=False):
+    hid = bf.HIDDEN if bf16 else None
+    x = torch.tanh(lin(x, p, "fc1", hid))
+    x = torch.tanh(lin(x, p, "fc2", hid))
+    return torch.tanh(lin(x, p, "fc3", hid)) * lim
 
 
 def basic_acm(p, x):

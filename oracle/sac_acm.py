@@ -21,10 +21,14 @@ from .adam import OracleAdam
 class OracleSacAcm:
     def __init__(self, ob, aout, ac, *, acm_critic=True, custom_loss=0.2, norm_closs=False,
                  norm=None, actor_lim=1.0, acm_lim=1.0, gamma=0.99, tau=0.005, actor_lr=1e-3,
-                 critic_lr=1e-3, alpha_lr=1e-3, alpha=0.2, target_entropy=None, params=None, dtype=torch.float32):
+                 critic_lr=1e-3, alpha_lr=1e-3, alpha=0.2, target_entropy=None, params=None, dtype=torch.float32,
+                 mlp_bf16=False):
         # dtype=torch.float64 gives a clean reference for the large-batch parity tests (the
         # device path is fp32; at B = 409,600 its summation order differs from torch's)
+        # mlp_bf16: every MLP layer rounds its matmul operands to bf16 where SAC_AcM(mlp_bf16=True)'s kernels
+        # do (oracle/bf16.py); the parameters stay the fp32 master, rounded at use
         self.dt = dtype
+        self.bf16 = bool(mlp_bf16)
         self.ob, self.aout, self.ac = ob, aout, ac
         self.acm_critic, self.custom_loss, self.norm_closs = acm_critic, custom_loss, norm_closs
         self.norm = norm
@@ -50,7 +54,7 @@ class OracleSacAcm:
         self.last = {}
 
     def _acm(self, x):
-        return nets.acm(self.p["acm"], x, self.acm_lim)
+        return nets.acm(self.p["acm"], x, self.acm_lim, self.bf16)
 
     def _t(self, a, dt=None):
         return torch.as_tensor(np.asarray(a)).to(self.dt if dt is None else dt)
@@ -63,18 +67,18 @@ class OracleSacAcm:
         done, acm_action, eps_next = t(done, torch.int8), t(acm_action), t(eps_next)
         P, losses = self.p, {}
         with torch.no_grad():
-            a2, lp2, _ = nets.sac_actor(P["actor"], next_obs, self.actor_lim, eps_next)
+            a2, lp2, _ = nets.sac_actor(P["actor"], next_obs, self.actor_lim, eps_next, self.bf16)
             a2 = self.norm.denormalize(a2)
             if self.acm_critic:
                 a2 = self._acm(torch.cat([next_obs, a2], axis=1))
-            q1t = nets.sac_critic(P["critic_1_targ"], next_obs, a2)
-            q2t = nets.sac_critic(P["critic_2_targ"], next_obs, a2)
+            q1t = nets.sac_critic(P["critic_1_targ"], next_obs, a2, self.bf16)
+            q2t = nets.sac_critic(P["critic_2_targ"], next_obs, a2, self.bf16)
             y = reward + self.gamma * (1 - done) * (torch.min(q1t, q2t) - self.alpha * lp2)
         if self.acm_critic:
             action = acm_action
         grads = {}
         for k in ("critic_1", "critic_2"):
-            q = nets.sac_critic(P[k], obs, action)
+            q = nets.sac_critic(P[k], obs, action, self.bf16)
             loss = F.mse_loss(q, y)
             losses[k] = loss.item()
             grads[k] = list(torch.autograd.grad(loss, list(P[k].values())))
@@ -90,10 +94,11 @@ class OracleSacAcm:
         t = self._t
         obs, next_obs, eps_cur = t(obs), t(next_obs), t(eps_cur)
         P, losses = self.p, {}
-        a, lp, _ = nets.sac_actor(P["actor"], obs, self.actor_lim, eps_cur)
+        a, lp, _ = nets.sac_actor(P["actor"], obs, self.actor_lim, eps_cur, self.bf16)
         ad = self.norm.denormalize(a)
         ca = self._acm(torch.cat([obs, ad], axis=1)) if self.acm_critic else ad
-        q = torch.min(nets.sac_critic(P["critic_1"], obs, ca), nets.sac_critic(P["critic_2"], obs, ca))
+        q = torch.min(nets.sac_critic(P["critic_1"], obs, ca, self.bf16),
+                      nets.sac_critic(P["critic_2"], obs, ca, self.bf16))
         loss = (self.alpha * lp - q).mean()
         losses["sac"], losses["dist"] = 0.0, 0.0
         if self.custom_loss:
@@ -139,3 +144,10 @@ class OracleSacAcm:
 
     def flat(self, k):
         return nets.flatten(self.p[k]).numpy()
+
+    def load_flat(self, k, flat):
+        """Overwrite network k's parameters (flat, state_dict order), e.g. with the device's post-step master."""
+        new = nets.unflatten(np.asarray(flat), self.layouts[k], dtype=self.dt)
+        with torch.no_grad():
+            for n, v in self.p[k].items():
+                v.copy_(new[n])

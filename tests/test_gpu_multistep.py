@@ -8,12 +8,18 @@ each of 3 consecutive updates (sac_acm.py:89-162, fresh batch and eps every step
     fp32 parameters its kernels consumed in that update (fp32 agents) or with torch's RNE bf16
     rounding of them (bf16 agents);
   - the post-step parameters of every network compared with the float64 oracle run on the same
-    batches (oracle/sac_acm.py): fp32 |d| <= 2 lr per step with < 0.2 % of weights beyond 1e-5 after
-    step 1 (Adam's first step moves each weight by ~lr sign(g): a gradient sign flip at the fp32
-    rounding level moves it by up to 2 lr); bf16 MLP (bf16 gradients, 8-bit mantissa) at B = 4,096 and
-    at the bench batch 409,600: |d| <= 2 lr per step, mean |d| <= 0.05 lr per step and at most 1 % of
-    the weights per step beyond lr (a sign flip; a wrong path flips about half of them);
-  - losses: fp32 rtol 1e-4, bf16 rtol 3e-2.
+    batches (oracle/sac_acm.py; bf16 agents: the bf16-rounding oracle, oracle/bf16.py, whose weights are the
+    fp32 master rounded at use, as the library's images are): |d| <= 2 lr per step with < 0.2 % of weights
+    beyond 1e-5 after step 1 (Adam's first step moves each weight by ~lr sign(g): a gradient sign flip at the
+    rounding level moves it by up to 2 lr); bf16 at B = 4,096 and at the bench batch 409,600 also
+    mean |d| <= 5e-3 lr per step and at most 2e-4 of the weights per step beyond lr;
+  - losses: rtol 1e-4, fp32 and bf16.
+Where the bf16 figures come from: the rounding oracle in float32 against itself in float64 over the same three
+steps (Ant, B = 512 and 4,096, four seeds) drifts by at most 3.2e-6 in a loss (x 4 is far below the fp32 path's
+1e-4, which therefore holds), by mean |d| = 1.2e-3 lr per step (x 4, rounded: 5e-3; was 0.05) and moves at most
+2e-5 of a network's weights per step beyond lr (one or two weights of 69k - 95k: the factor is 10 instead of 4 for
+the spread of so small a count: 2e-4; was 0.01), and leaves at most 1.1e-4 of the weights beyond 1e-5 after step 1
+(x 4 is inside the fp32 rule's 2e-3, applied to bf16 as well now).
 """
 import numpy as np
 import pytest
@@ -70,7 +76,7 @@ def test_three_updates_images_and_params_match_oracle(env_name, ob, ac, B, bf16)
     params = snapshot(ag, SAC_NETS)
     norm = set_minmax(ag, rng, ob)
     o = OracleSacAcm(ob, ob, ac, acm_critic=True, custom_loss=0.2, norm_closs=False, norm=norm, actor_lim=1.0,
-                     acm_lim=np.ones(ac, np.float32), gamma=0.99, params=params, dtype=torch.float64)
+                     acm_lim=np.ones(ac, np.float32), gamma=0.99, params=params, dtype=torch.float64, mlp_bf16=bf16)
     for step in range(1, steps + 1):
         batch = random_batch(rng, B, ob, ob, ac)
         e1, e2 = rng.randn(B, ob).astype(np.float32), rng.randn(B, ob).astype(np.float32)
@@ -80,22 +86,24 @@ def test_three_updates_images_and_params_match_oracle(env_name, ob, ac, B, bf16)
         ol = o.update(*batch, e1, e2)
         nimg = check_images(ag, bf16, before)
         gl = ag.loss
-        tol = 3e-2 if bf16 else 1e-4
-        for k in ("critic_1", "critic_2", "actor"):
-            assert abs(gl[k] - ol[k]) <= tol * abs(ol[k]) + 1e-6, (step, k, gl[k], ol[k])
-        stats = {}
+        stats, dmax = {}, {}
         for k in ("actor", "critic_1", "critic_2", "critic_1_targ", "critic_2_targ"):
             got = ag.params[SAC_NETS[k]].cpu().numpy().astype(np.float64)
             d = np.abs(got - o.flat(k).astype(np.float64))
             stats[k] = (d.max() / lr, d.mean() / lr, float(np.mean(d > 1e-5)), float(np.mean(d > lr)))
-            assert d.max() <= 2 * lr * step * 1.01, (step, k, d.max())
+            dmax[k] = d.max()
+        print("step %d: %d images exact; loss rel err" % (step, nimg),
+              {k: "%.1e" % (abs(gl[k] - ol[k]) / abs(ol[k])) for k in ("critic_1", "critic_2", "actor")},
+              "|d|/lr max, mean, frac>1e-5, frac>lr:", {k: tuple("%.2e" % x for x in v) for k, v in stats.items()})
+        for k in ("critic_1", "critic_2", "actor"):
+            assert abs(gl[k] - ol[k]) <= 1e-4 * abs(ol[k]) + 1e-6, (step, k, gl[k], ol[k])
+        for k, (_, mean_lr, frac_1e5, frac_lr) in stats.items():
+            assert dmax[k] <= 2 * lr * step * 1.01, (step, k, dmax[k])
             if bf16:
                 # |d| <= 2 lr per step is saturated by any one sign flip; these two can fail: a wrong operand
                 # or gradient moves ~half the weights by 2 lr (mean ~lr, fraction beyond lr ~0.5)
-                assert d.mean() <= 0.05 * lr * step, (step, k, d.mean())
-                assert np.mean(d > lr) <= 0.01 * step, (step, k, np.mean(d > lr))
-            elif step == 1:
-                assert np.mean(d > 1e-5) < 2e-3, (k, np.mean(d > 1e-5))
-        print("step %d: %d images exact; |d|/lr max, mean, frac>1e-5, frac>lr:" % (step, nimg),
-              {k: tuple(round(x, 4) for x in v) for k, v in stats.items()})
-        assert ag.current_alpha() == pytest.approx(o.alpha, rel=1e-4 if not bf16 else 1e-2)
+                assert mean_lr <= 5e-3 * step, (step, k, mean_lr)
+                assert frac_lr <= 2e-4 * step, (step, k, frac_lr)
+            if step == 1:
+                assert frac_1e5 < 2e-3, (k, frac_1e5)
+        assert ag.current_alpha() == pytest.approx(o.alpha, rel=1e-4)

@@ -9,6 +9,7 @@ import torch
 
 import spprl
 from spprl import _lib
+from bf16_cases import assert_tensor_grads, fp32_elem_tol
 from golden_cases import sac_vanilla_case
 from oracle.sac import OracleSac, policy_act
 
@@ -155,6 +156,8 @@ def test_vanilla_sac_team_kernels_match_float64_oracle(B, monkeypatch):
             g = ag.grads[NAMES[k]].cpu().numpy()
             e = relerr(g, o.last["grads"][k])
             assert e < 2e-4, (team, k, e)
+            assert_tensor_grads(g, o.last["grads"][k], o.layouts[k], 2e-4, "team=%s %s" % (team, k),
+                                fp32_elem_tol(B))
             assert ag.loss[k] == pytest.approx(ol[k], rel=1e-4, abs=1e-6), (team, k)
             grads[team, k] = g
     assert any(not np.array_equal(grads["1", k], grads["0", k]) for k in ("critic_1", "critic_2", "actor"))
