@@ -103,8 +103,6 @@ def _compile(src, verbose):
 # the ones below: (name fragment, scratch bytes per lane at most), each covered by a phase-level GPU parity
 # test at the bench sizes (DESIGN.md §8 lists them and the tests).  A new or grown scratch user is an error.
 SCRATCH_ALLOWED = {
-    # SAC_AcM HalfCheetah actor phase with acm_critic (4 VGPRs; tests: test_gpu_parity sac_hcheetah_paper fixture)
-    "k_sac_actor_phaseINS_3CfgILi17ELi17ELi6ELb1ELb0EEE": 12,
     # DDPG_AcM Ant (111-dim obs) actor phase / policy act (3-4 VGPRs; test_gpu_ddpg test_ddpg_acm_ant_dims_match_oracle)
     "k_ddpg_actor_phaseINS_4DCfgILi111ELi111ELi8ELb1EEE": 16,
     "k_ddpg_policy_actINS_4DCfgILi111ELi111ELi8EL": 20,

@@ -21,6 +21,16 @@
 #define SPP_BF16_FUSE3 0
 #endif
 
+// fp32 narrow-input kernel sets: input blocks of the 256-wide layers produced in registers inside the
+// consumer's MFMA loop (dense_gen, mlp.h) instead of staged through the wave's LDS image.  One bit per
+// hand-over, so each can be A/B'd on its own; 0 compiles the staged code.
+//   1  critic phase: delta2 -> W2^T      2  actor phase: each critic's delta2 -> W2^T
+//   4  critic_forward: fc1 -> fc2
+// (The actor trunk's fc1 -> fc2 was tried as a fourth bit and is not shipped: DESIGN.md §8.)
+#ifndef SPP_GEN_INPUTS
+#define SPP_GEN_INPUTS 7
+#endif
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

@@ -254,24 +254,33 @@ __global__ __launch_bounds__(256, 1) void k_ddpg_critic_phase(SacArgs p, BAcmScr
     }
     const rsrc_t d2r = rsrc(p.D2[0]);
     const float* w3 = tbl + Q.tw3;
-#pragma unroll 1
-    for (int ob = 0; ob < 8; ++ob) {
-      float tv[16];
-      tvals(w3, ob, L.h4, tv);
-#pragma unroll
-      for (int q2 = 0; q2 < 16; ++q2) {
-        const int ur = 32 * ob + ru(q2);
-        const float v = getbit(m2lo, m2hi, ob, q2) ? dq * tv[q2] : 0.f;
-        L.bl[ur * 32] = v;
-        fm_st(d2r, ur, L.ld4, L.vo, v);
-      }
-    }
     const rsrc_t d1r = rsrc(p.D1[0]);
-    dense_lds<8>(Q.W2T, big, nullptr, [&](int ob, const f32x16& acc) {
+    auto epi1 = [&](int ob, const f32x16& acc) {
 #pragma unroll
       for (int q2 = 0; q2 < 16; ++q2)
         fm_st(d1r, 32 * ob + ru(q2), L.ld4, L.vo, getbit(m1lo, m1hi, ob, q2) ? acc[q2] : 0.f);
-    });
+    };
+    if constexpr (C::GEN_CD2) {  // delta2 produced in registers under the W2^T MFMAs (sac.hip's Delta2Gen)
+      const int ld4 = L.ld4;
+      const uint32_t vo = L.vo;
+      auto st2 = [=](int ur, float v) { fm_st(d2r, ur, ld4, vo, v); };
+      Delta2Gen<8, decltype(st2)> g{w3, L.h4, m2lo, m2hi, dq, st2, {}};
+      dense_gen<8>(Q.W2T, nullptr, g, epi1);
+    } else {
+#pragma unroll 1
+      for (int ob = 0; ob < 8; ++ob) {
+        float tv[16];
+        tvals(w3, ob, L.h4, tv);
+#pragma unroll
+        for (int q2 = 0; q2 < 16; ++q2) {
+          const int ur = 32 * ob + ru(q2);
+          const float v = getbit(m2lo, m2hi, ob, q2) ? dq * tv[q2] : 0.f;
+          L.bl[ur * 32] = v;
+          fm_st(d2r, ur, L.ld4, L.vo, v);
+        }
+      }
+      dense_lds<8>(Q.W2T, big, nullptr, epi1);
+    }
     const float s0 = wave_sum(lq);
     if (lane == 0) p.part[tile * kParts + 0] = s0;
   }
@@ -332,17 +341,24 @@ __global__ __launch_bounds__(256, 1) void k_ddpg_actor_phase(SacArgs p, BAcmScra
     const float dqv = valid ? -p.inv_B : 0.f;
     // ---- back through the critic to its action input
     const float* w3 = tbl + Q.tw3;
-#pragma unroll 1
-    for (int ob = 0; ob < 8; ++ob) {
-      float tv[16];
-      tvals(w3, ob, L.h4, tv);
-#pragma unroll
-      for (int q2 = 0; q2 < 16; ++q2) L.bl[(32 * ob + ru(q2)) * 32] = getbit(k2, k3, ob, q2) ? dqv * tv[q2] : 0.f;
-    }
-    dense_lds<8>(Q.W2T, big, nullptr, [&](int ob, const f32x16& acc) {
+    auto epi1 = [&](int ob, const f32x16& acc) {
 #pragma unroll
       for (int q2 = 0; q2 < 16; ++q2) L.bl[(32 * ob + ru(q2)) * 32] = getbit(k0, k1, ob, q2) ? acc[q2] : 0.f;
-    });
+    };
+    if constexpr (C::GEN_AD2) {  // delta2 produced in registers under the W2^T MFMAs
+      auto st2 = [](int, float) {};
+      Delta2Gen<8, decltype(st2)> g{w3, L.h4, k2, k3, dqv, st2, {}};
+      dense_gen<8>(Q.W2T, nullptr, g, epi1);
+    } else {
+#pragma unroll 1
+      for (int ob = 0; ob < 8; ++ob) {
+        float tv[16];
+        tvals(w3, ob, L.h4, tv);
+#pragma unroll
+        for (int q2 = 0; q2 < 16; ++q2) L.bl[(32 * ob + ru(q2)) * 32] = getbit(k2, k3, ob, q2) ? dqv * tv[q2] : 0.f;
+      }
+      dense_lds<8>(Q.W2T, big, nullptr, epi1);
+    }
     f32x16 dca[C::NB_CA];
 #pragma unroll
     for (int ib = 0; ib < C::NB_CA; ++ib) dca[ib] = zero16();

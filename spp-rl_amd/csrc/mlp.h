@@ -385,6 +385,91 @@ __device__ __forceinline__ void dense_lds_impl(const float4* __restrict__ Wf, co
   SPP_TPD(22);
 }
 
+// Register-input form of the 256-input layer (fp32): dense_lds_impl with the LDS image reads
+// replaced by a generator.  The D layout of an output block is the input-block layout of the next
+// layer, so a block the wave can produce in registers (fc1's ReLU output, the rank-one delta2 =
+// dq * w3 * relu'(h2)) is handed to the layer as xin directly, without the image round trip, and
+// the producer's VALU / LDS-table / store work issues beside the layer's MFMAs instead of in a bare
+// loop in front of them.  Same fragment ring, chunk order, peeled last block and epilogue placement
+// as dense_lds_impl, hence the same products in the same accumulation order.
+// A wave issues in order and is alone on its SIMD, so producer work only overlaps MFMAs it stands
+// between in program order: the generator is called in NBO parts per input block,
+//     gen(ib, IC<part>{}, x),  part = 0 .. NBO-1, in this order, ib = 0 .. 7 in this order,
+// part u of block ib+1 after chunk u's MFMAs of block ib (the ring's scheduling barriers keep each
+// part between its two chunks).  After the last part x holds all 16 registers of block ib.  Block 0
+// is produced in the prologue.  gen may keep state between its calls (it is called on an lvalue).
+// The layer itself never touches the image; epi may write it.
+template <int NBO, bool BIAS, typename Gen, typename Epi>
+__device__ __forceinline__ void dense_gen_impl(const float4* __restrict__ Wf, const float* biasL, Gen&& gen,
+                                               Epi&& epi) {
+  constexpr int CH = 4;        // float4 per chunk
+  constexpr int NCI = NBO;     // chunks per input block
+  constexpr int D = 4;         // ring depth (chunks)
+  constexpr int G = 8 * NCI;   // chunks in the layer
+  static_assert(NCI % D == 0, "one input block per loop iteration");
+  const int lane = lane_id();
+  const int h = lane >> 5;
+  const rsrc_t wr = rsrc(Wf);
+  const uint32_t l16 = 16u * lane;
+  f32x16 acc[NBO];
+  static_for<0, NBO>([&](auto O) {
+    if constexpr (BIAS) acc[O] = bias_tile(biasL, O, h);
+    else acc[O] = zero16();
+  });
+  float4 ring[D][CH];
+  static_for<0, D - 1>([&](auto I) {
+    static_for<0, CH>([&](auto J) { ring[I][J] = wfrag(wr, l16, ((int)I * CH + (int)J) * 1024); });
+  });
+  f32x16 xin;
+  static_for<0, NCI>([&](auto P) { gen(0, P, xin); });
+  auto step = [&](auto UC, int it) {
+    constexpr int u = UC;
+    constexpr int sn = (u + D - 1) % D;
+    const int gn = it * NCI + u + D - 1;
+    if (gn < G) {
+      static_for<0, CH>([&](auto J) { ring[sn][J] = wfrag(wr, l16, (gn * CH + (int)J) * 1024); });
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    constexpr int s = u % D;
+    static_for<0, CH>([&](auto J) {
+      constexpr int rq = J;
+      acc[u] = mfma(ring[s][J].x, xin[4 * rq + 0], acc[u]);
+      acc[u] = mfma(ring[s][J].y, xin[4 * rq + 1], acc[u]);
+      acc[u] = mfma(ring[s][J].z, xin[4 * rq + 2], acc[u]);
+      acc[u] = mfma(ring[s][J].w, xin[4 * rq + 3], acc[u]);
+    });
+  };
+  SPP_TPD(20);
+#pragma unroll 1
+  for (int it = 0; it < 7; ++it) {
+    f32x16 xnx;
+    static_for<0, NCI>([&](auto UC) {
+      step(UC, it);
+      gen(it + 1, UC, xnx);
+    });
+    xin = xnx;
+  }
+  static_for<0, NCI>([&](auto UC) {
+    step(UC, 7);
+    constexpr int u = UC;
+    if constexpr (u >= 1) epi(IC<u - 1>{}, acc[u - 1]);
+  });
+  SPP_TPD(21);
+  epi(IC<NBO - 1>{}, acc[NBO - 1]);
+  SPP_TPD(22);
+}
+template <int NBO, typename Gen, typename Epi>
+__device__ __forceinline__ void dense_gen(const float4* __restrict__ Wf, const float* biasL, Gen&& gen, Epi&& epi) {
+  dense_gen_impl<NBO, true>(Wf, biasL, gen, static_cast<Epi&&>(epi));
+}
+template <int NBO, typename Gen, typename Epi>
+__device__ __forceinline__ void dense_gen(const float4* __restrict__ Wf, decltype(nullptr), Gen&& gen, Epi&& epi) {
+  dense_gen_impl<NBO, false>(Wf, nullptr, gen, static_cast<Epi&&>(epi));
+}
+// Registers [gen_q0(part), gen_q0(part + 1)) of a block: the share of part >= 1 when a generator
+// spends part 0 on its loads / MFMA chain and spreads the 16 registers over the other NP - 1 parts.
+constexpr int gen_q0(int part, int NP) { return part <= 0 ? 0 : 16 * (part - 1) / (NP - 1); }
+
 // ---------------------------------------------------------------- bf16 MFMA layers
 // v_mfma_f32_32x32x16_bf16: lane (i = l&31, h = l>>5) holds A[i][k = 8h + j] and
 // B[k = 8h + j][i], j = 0..7; D layout as the f32 form.  The input tile's registers

@@ -43,6 +43,14 @@ struct Cfg {
   static constexpr uint64_t RV_AC = rv_nat(AC, 1);
   static constexpr uint64_t RV_CA = rv_nat(CA, NB_CA);
   static constexpr uint64_t RV_PAIR = rv_pair(AOUT, NB_PAIR);
+  // Input blocks of the 256-wide layers produced in registers inside the consumer's MFMA loop (dense_gen)
+  // instead of staged through the LDS image (SPP_GEN_INPUTS, common.h): the fp32 sets whose critic input is
+  // one observation block and one action block.  The wide-input sets (111-dim observations, NB_CIN = 5)
+  // spill VGPRs to scratch with the generators' state and keep the staged path.
+  static constexpr bool kGenOk = !BF_ && NB_OB == 1 && NB_CA == 1;
+  static constexpr bool GEN_CD2 = kGenOk && (SPP_GEN_INPUTS & 1);   // critic phase: delta2 -> W2^T
+  static constexpr bool GEN_AD2 = kGenOk && (SPP_GEN_INPUTS & 2);   // actor phase: delta2 -> W2^T
+  static constexpr bool GEN_CFC1 = kGenOk && (SPP_GEN_INPUTS & 4);  // critic_forward: fc1 -> fc2
   static_assert(AC <= 32, "env action dim <= 32");
   static_assert(2 * AOUT <= 256 && OB + AOUT <= 256, "dims");
 };
@@ -246,6 +254,85 @@ __device__ __forceinline__ Lane make_lane(float* big, float* small, const float*
   return L;
 }
 
+// ---- generators of dense_gen's input blocks (mlp.h: called in NP parts per block, in order)
+// delta2 = dq * w3 * relu'(h2) of a critic, rank one per sample: register q of block ib is
+// mask bit (ib, q) ? dq * w3[unit] : 0.  Part 0 reads the block's 16 table values, the other parts
+// spread the registers; st(unit row, value) stores the weight-gradient operand (or does nothing).
+template <int NP, typename St>
+struct Delta2Gen {
+  const float* w3;
+  int h4;
+  uint64_t lo, hi;
+  float dq;
+  St st;
+  float tv[16];
+  template <int P>
+  __device__ __forceinline__ void operator()(int ib, IC<P>, f32x16& x) {
+    if constexpr (P == 0) {
+      tvals(w3, ib, h4, tv);
+    } else {
+#pragma unroll
+      for (int q = gen_q0(P, NP); q < gen_q0(P + 1, NP); ++q) {
+        const float v = getbit(lo, hi, ib, q) ? dq * tv[q] : 0.f;
+        x[q] = v;
+        st(32 * ib + ru(q), v);
+      }
+    }
+  }
+};
+// relu(fc1) of a register-input first layer (dense_impl's chain: bias tile, then the register quads in
+// flat order) as the input of fc2.  Part 0 runs block ib's MFMA chain and then requests block ib+1's
+// fragments into the same registers, so their L2 latency sits under the consumer's MFMAs; the other
+// parts spread the ReLU, the mask bits and st(unit row, value), the h1 operand store (or nothing).
+template <int NBI, uint64_t RV, int NP, typename St>
+struct Fc1Gen {
+  static constexpr int NQ = rv_total(RV, NBI);
+  static constexpr int OBSTRIDE = NBI * 4 * 64 * 16;  // bytes per output block
+  const f32x16 (&in)[NBI];
+  rsrc_t wr;
+  uint32_t l16;
+  const float* biasL;
+  int h;
+  uint64_t &mlo, &mhi;
+  St st;
+  float4 cur[NQ];
+  f32x16 acc;
+  uint32_t bits;
+  __device__ __forceinline__ void request(int ob) {
+    const int wn = ob * OBSTRIDE;
+    static_for<0, NQ>([&](auto Q) {
+      constexpr int q = Q;
+      cur[q] = wfrag(wr, l16, wn + (q_ib(RV, NBI, q) * 4 + q_rq(RV, NBI, q)) * 1024);
+    });
+  }
+  template <int P>
+  __device__ __forceinline__ void operator()(int ib, IC<P>, f32x16& x) {
+    if constexpr (P == 0) {
+      acc = bias_tile(biasL, ib, h);
+      static_for<0, NQ>([&](auto Q) {
+        constexpr int q = Q;
+        constexpr int kb = q_ib(RV, NBI, q);
+        constexpr int rq = q_rq(RV, NBI, q);
+        acc = mfma(cur[q].x, in[kb][4 * rq + 0], acc);
+        acc = mfma(cur[q].y, in[kb][4 * rq + 1], acc);
+        acc = mfma(cur[q].z, in[kb][4 * rq + 2], acc);
+        acc = mfma(cur[q].w, in[kb][4 * rq + 3], acc);
+      });
+      request(ib + 1 < 8 ? ib + 1 : ib);  // (the last block re-reads its own: no branch in the MFMA loop)
+      bits = 0;
+    } else {
+#pragma unroll
+      for (int q = gen_q0(P, NP); q < gen_q0(P + 1, NP); ++q) {
+        const float v = fmaxf(acc[q], 0.f);
+        x[q] = v;
+        st(32 * ib + ru(q), v);
+        bits |= (uint32_t)(v > 0.f) << q;
+      }
+      if constexpr (P == NP - 1) setbits(mlo, mhi, ib, bits);
+    }
+  }
+};
+
 // Actor trunk: x -> relu(L1) -> relu(L2) -> heads into LDS rows [0, NHR): SAC
 // (mu | logsig), NHR = 2*AOUT; DDPG fc3 pre-activation, NHR = AOUT (NBH blocks).
 // ST: store h1 / h2 feature-major (H1g, H2g).  Returns the ReLU masks.
@@ -355,22 +442,9 @@ __device__ __forceinline__ float critic_forward(const CriticDev& Q, const f32x16
                                                 float* H1g, float* H2g, uint64_t& m1lo, uint64_t& m1hi,
                                                 uint64_t& m2lo, uint64_t& m2hi) {
   const rsrc_t h1r = rsrc(H1g), h2r = rsrc(H2g);
-  dense<C::NB_CIN, C::RV_CIN, C::BF>(Q.W1, 8, xin, L.tbl + Q.tb1, [&](int ob, const f32x16& acc) {
-    uint32_t bits = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int ur = 32 * ob + ru(q);
-      const float v = fmaxf(acc[q], 0.f);
-      L.bl[ur * 32] = v;
-      if constexpr (ST) op_st<C::BF>(h1r, ur, L.ld4, L.vo, v);
-      bits |= (uint32_t)(v > 0.f) << q;
-    }
-    setbits(m1lo, m1hi, ob, bits);
-  });
-  SPP_TP(R);
   float qp = 0.f;
   const float* w3 = L.tbl + Q.tw3;
-  dense_lds<8, C::BF>(Q.W2, L.img, L.tbl + Q.tb2, [&](int ob, const f32x16& acc) {
+  auto epi2 = [&](int ob, const f32x16& acc) {
     uint32_t bits = 0;
     float tv[16];
     tvals(w3, ob, L.h4, tv);
@@ -383,7 +457,34 @@ __device__ __forceinline__ float critic_forward(const CriticDev& Q, const f32x16
       bits |= (uint32_t)(v > 0.f) << q;
     }
     setbits(m2lo, m2hi, ob, bits);
-  });
+  };
+  if constexpr (C::GEN_CFC1) {
+    // fc1's blocks are produced in registers under fc2's MFMAs (Fc1Gen): the layer does not touch the image
+    const int ld4 = L.ld4;
+    const uint32_t vo = L.vo;
+    auto st1 = [=](int ur, float v) {
+      if constexpr (ST) op_st<C::BF>(h1r, ur, ld4, vo, v);
+    };
+    Fc1Gen<C::NB_CIN, C::RV_CIN, 8, decltype(st1)> g{xin, rsrc(Q.W1), 16u * lane_id(), L.tbl + Q.tb1, L.h, m1lo, m1hi, st1};
+    g.request(0);
+    SPP_TP(R);
+    dense_gen<8>(Q.W2, L.tbl + Q.tb2, g, epi2);
+  } else {
+    dense<C::NB_CIN, C::RV_CIN, C::BF>(Q.W1, 8, xin, L.tbl + Q.tb1, [&](int ob, const f32x16& acc) {
+      uint32_t bits = 0;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int ur = 32 * ob + ru(q);
+        const float v = fmaxf(acc[q], 0.f);
+        L.bl[ur * 32] = v;
+        if constexpr (ST) op_st<C::BF>(h1r, ur, L.ld4, L.vo, v);
+        bits |= (uint32_t)(v > 0.f) << q;
+      }
+      setbits(m1lo, m1hi, ob, bits);
+    });
+    SPP_TP(R);
+    dense_lds<8, C::BF>(Q.W2, L.img, L.tbl + Q.tb2, epi2);
+  }
   SPP_TP(R + 1);
   return qp + __shfl_xor(qp, 32, 64) + *Q.b3;
 }
@@ -534,29 +635,40 @@ __global__ __launch_bounds__(256, 1) void k_sac_critic_phase(SacArgs p) {
       else b3b += dsum;
       SPP_XLANE_SYNC();  // the image rows are rewritten by the delta2 staging below
       }
-      // delta2 = dq * w3 * relu'(h2): staged through the LDS image, stored feature-major
       const rsrc_t d2r = rsrc(p.D2[i]);
       const float* w3 = tbl + Q.tw3;
-#pragma unroll 1
-      for (int ob = 0; ob < 8; ++ob) {
-        float tv[16];
-        tvals(w3, ob, L.h4, tv);
-#pragma unroll
-        for (int q2 = 0; q2 < 16; ++q2) {
-          const int ur = 32 * ob + ru(q2);
-          const float v = getbit(m2lo, m2hi, ob, q2) ? dq * tv[q2] : 0.f;
-          L.bl[ur * 32] = v;
-          op_st<C::BF>(d2r, ur, L.ld4, L.vo, v);
-        }
-      }
-      SPP_TP(13);
       // delta1 = (W2^T delta2) * relu'(h1)
       const rsrc_t d1r = rsrc(p.D1[i]);
-      dense_lds<8, C::BF>(Q.W2T, big, nullptr, [&](int ob, const f32x16& acc) {
+      auto epi1 = [&](int ob, const f32x16& acc) {
 #pragma unroll
         for (int q2 = 0; q2 < 16; ++q2)
           op_st<C::BF>(d1r, 32 * ob + ru(q2), L.ld4, L.vo, getbit(m1lo, m1hi, ob, q2) ? acc[q2] : 0.f);
-      });
+      };
+      if constexpr (C::GEN_CD2) {
+        // delta2 = dq * w3 * relu'(h2): produced in registers under the W2^T MFMAs, stored feature-major
+        const int ld4 = L.ld4;
+        const uint32_t vo = L.vo;
+        auto st2 = [=](int ur, float v) { op_st<C::BF>(d2r, ur, ld4, vo, v); };
+        Delta2Gen<8, decltype(st2)> g{w3, L.h4, m2lo, m2hi, dq, st2, {}};
+        SPP_TP(13);
+        dense_gen<8>(Q.W2T, nullptr, g, epi1);
+      } else {
+        // delta2 = dq * w3 * relu'(h2): staged through the LDS image, stored feature-major
+#pragma unroll 1
+        for (int ob = 0; ob < 8; ++ob) {
+          float tv[16];
+          tvals(w3, ob, L.h4, tv);
+#pragma unroll
+          for (int q2 = 0; q2 < 16; ++q2) {
+            const int ur = 32 * ob + ru(q2);
+            const float v = getbit(m2lo, m2hi, ob, q2) ? dq * tv[q2] : 0.f;
+            L.bl[ur * 32] = v;
+            op_st<C::BF>(d2r, ur, L.ld4, L.vo, v);
+          }
+        }
+        SPP_TP(13);
+        dense_lds<8, C::BF>(Q.W2T, big, nullptr, epi1);
+      }
     }
     SPP_TP(14);
     const float s0 = wave_sum(lq0), s1 = wave_sum(lq1);
@@ -666,18 +778,26 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
       const uint64_t k0 = i ? mb0 : ma0, k1 = i ? mb1 : ma1, k2 = i ? mb2 : ma2, k3 = i ? mb3 : ma3;
       const float dqi = i ? dqb : dqa;
       const float* w3 = tbl + Q.tw3;
-#pragma unroll 1
-      for (int ob = 0; ob < 8; ++ob) {
-        float tv[16];
-        tvals(w3, ob, L.h4, tv);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) L.bl[(32 * ob + ru(q)) * 32] = getbit(k2, k3, ob, q) ? dqi * tv[q] : 0.f;
-      }
-      SPP_TPN(20);  // delta staging
-      dense_lds<8, C::BF>(Q.W2T, big, nullptr, [&](int ob, const f32x16& acc) {
+      auto epi1 = [&](int ob, const f32x16& acc) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) L.bl[(32 * ob + ru(q)) * 32] = getbit(k0, k1, ob, q) ? acc[q] : 0.f;
-      });
+      };
+      if constexpr (C::GEN_AD2) {
+        auto st2 = [](int, float) {};
+        Delta2Gen<8, decltype(st2)> g{w3, L.h4, k2, k3, dqi, st2, {}};
+        SPP_TPN(20);  // (delta2 is produced under the W2T MFMAs)
+        dense_gen<8>(Q.W2T, nullptr, g, epi1);
+      } else {
+#pragma unroll 1
+        for (int ob = 0; ob < 8; ++ob) {
+          float tv[16];
+          tvals(w3, ob, L.h4, tv);
+#pragma unroll
+          for (int q = 0; q < 16; ++q) L.bl[(32 * ob + ru(q)) * 32] = getbit(k2, k3, ob, q) ? dqi * tv[q] : 0.f;
+        }
+        SPP_TPN(20);  // delta staging
+        dense_lds<8, C::BF>(Q.W2T, big, nullptr, epi1);
+      }
       SPP_TPN(21);  // W2T
       dense_lds<C::NB_CA, C::BF>(Q.W1Ta, big, nullptr, [&](int ob, const f32x16& acc) {
 #pragma unroll

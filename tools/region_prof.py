@@ -13,15 +13,22 @@ import torch  # noqa: E402
 import spprl  # noqa: E402
 from spprl import _lib  # noqa: E402
 
+# Kernel sets built with the register hand-over (SPP_GEN_INPUTS, csrc/common.h; the fp32 narrow-input sets) produce
+# the critics' fc1 output and delta2 inside the consumer layer: the "L1" regions then hold only the first fragment
+# request, the "delta staging" regions nothing, and their work is counted in the following L2 / W2T region.
 NAMES = {0: "tile start", 1: "actor L1", 2: "actor L2", 3: "actor heads", 4: "squash", 5: "ACM + target input",
-         6: "targ1 L1", 7: "targ1 L2", 8: "targ2 L1", 9: "targ2 L2", 10: "y + critic input", 11: "critic L1",
-         12: "critic L2", 13: "delta2 staging", 14: "critic W2T", 15: "tile end",
-         20: "dense_lds prologue | A: delta staging (nodense)", 21: "dense_lds loop | A: W2T (nodense)",
+         6: "targ1 L1 (gen: request only)", 7: "targ1 L2 (gen: + L1)", 8: "targ2 L1 (gen: request only)",
+         9: "targ2 L2 (gen: + L1)", 10: "y + critic input", 11: "critic L1 (gen: request only)",
+         12: "critic L2 (gen: + L1)", 13: "delta2 staging (gen: fc3 gradient only)", 14: "critic W2T (gen: + delta2)",
+         15: "tile end",
+         20: "dense_lds prologue | A: delta staging (nodense; gen: none)",
+         21: "dense_lds loop | A: W2T (nodense; gen: + delta2)",
          22: "dense_lds epilogue | A: W1Ta (nodense)",
          23: "dense prologue | A: ACM bwd input (nodense)", 24: "dense mfma | A: ACM W3T (nodense)",
          25: "dense epilogue | A: ACM W2T (nodense)",
          26: "A: tile start", 27: "A: actor trunk", 28: "A: squash", 29: "A: ACM fwd", 19: "A: q min",
-         30: "A: critics L1 (fwd)", 31: "A: critics L2 (fwd)", 16: "A: ACM bwd", 17: "A: heads bwd", 18: "A: trunk bwd"}
+         30: "A: critics L1 (fwd; gen: request only)", 31: "A: critics L2 (fwd; gen: + L1)", 16: "A: ACM bwd",
+         17: "A: heads bwd", 18: "A: trunk bwd"}
 
 
 def main():
