@@ -158,8 +158,12 @@ sppStatus sppReplayLastRollout(sppReplayHandle h, int64_t* first, int64_t* lengt
 
 /* ------------------------------------------------------------------ agent */
 /* SPP_ALGO_SAC: vanilla SAC (rltoolkit/algorithms/sac/sac.py:138-280), BASELINE configs[0]: no ACM,
- * the actor emits the env action (aout == ac) and feeds the critics directly. */
-enum { SPP_ALGO_SAC_ACM = 1, SPP_ALGO_DDPG_ACM = 2, SPP_ALGO_SAC = 3 };
+ * the actor emits the env action (aout == ac) and feeds the critics directly.
+ * SPP_ALGO_DDPG: vanilla DDPG (rltoolkit/algorithms/ddpg/ddpg.py:171-327, train/vanilla_ddpg_hcheetah.py):
+ * the deterministic actor and its target emit the env action (aout == ac), one critic and its target on
+ * cat(obs, action), no ACM network (SPP_NET_ACM has size 0 and is never bound or read).  Driven through
+ * the sppDdpgAcm* entry points. */
+enum { SPP_ALGO_SAC_ACM = 1, SPP_ALGO_DDPG_ACM = 2, SPP_ALGO_SAC = 3, SPP_ALGO_DDPG = 4 };
 enum { /* network ids for parameter binding (SAC_AcM) */
   SPP_NET_ACTOR = 0, SPP_NET_CRITIC1 = 1, SPP_NET_CRITIC2 = 2,
   SPP_NET_CRITIC1_TARG = 3, SPP_NET_CRITIC2_TARG = 4, SPP_NET_ACM = 5,
@@ -168,7 +172,9 @@ enum { /* network ids for parameter binding (SAC_AcM) */
 };
 
 typedef struct {
-  int algo;                 /* SPP_ALGO_SAC_ACM (ACM = AcM 64-32) | SPP_ALGO_DDPG_ACM (ACM = BasicAcM) */
+  int algo;                 /* SPP_ALGO_SAC_ACM (ACM = AcM 64-32) | SPP_ALGO_DDPG_ACM (ACM = BasicAcM) |
+                             * SPP_ALGO_SAC | SPP_ALGO_DDPG (vanilla: no ACM; aout == ac, acm_critic = 0,
+                             * custom_loss = 0) */
   int ob, aout, ac;         /* obs dim, actor output dim (= len(acm_ob_idx) = ob), env action dim */
   int acm_critic;           /* critics see ACM(s, denorm a) (ac) instead of denorm a (aout) */
   int min_max_denormalize;  /* memory.py:107-121 min-max vs z-score */

@@ -39,6 +39,7 @@
 #include "ks_ddpg_ant.hip"
 #include "ks_sac_bf16.hip"
 #include "ks_sac_vanilla.hip"
+#include "ks_ddpg_vanilla.hip"
 #endif
 #endif
 #include "onp.hip"
@@ -805,6 +806,13 @@ static bool find_kset(int algo, int ob, int aout, int ac, bool acmc, bool bf16, 
     return false;
 #endif
   }
+  if (algo == SPP_ALGO_DDPG) {
+#ifndef SPP_ONLY_HOPPER
+    return kset_ddpg_vanilla(ob, aout, ac, acmc, ks);
+#else
+    return false;
+#endif
+  }
   if (algo == SPP_ALGO_SAC_ACM) {
     if (kset_sac_hopper(ob, aout, ac, acmc, ks)) return true;
 #if defined(SPP_ONLY_HOPPER) && defined(SPP_WITH_HCHEETAH)
@@ -841,7 +849,9 @@ struct sppAgent {
   DevArray<float4> pk;     // all matrix images
   std::vector<PackJob> pj_actor, pj_acm, pj_targ, pj_critic_fwd, pj_critic_all, pj_acmreg;
   bool ddpg = false;
-  bool plain = false;  // vanilla SAC (SPP_ALGO_SAC): the ACM net exists but is never evaluated
+  // vanilla SAC (SPP_ALGO_SAC): the ACM net exists but is never evaluated; vanilla DDPG (SPP_ALGO_DDPG,
+  // ddpg && plain): there is no ACM net at all
+  bool plain = false;
   DevArray<PackJob> d_pj;
   // job-table offsets inside d_pj
   int o_actor = 0, o_acm = 0, o_targ = 0, o_cfwd = 0, o_call = 0, o_acmreg = 0;
@@ -922,7 +932,7 @@ static sppStatus build_packs(sppAgent* a) {
   const int cin = ob + ca;
   for (int k = 0; k < SPP_NET_COUNT; ++k) {
     const bool used = a->ddpg ? (k == SPP_NET_ACTOR || k == SPP_NET_CRITIC1 || k == SPP_NET_CRITIC1_TARG ||
-                                 k == SPP_NET_ACM || k == SPP_NET_ACTOR_TARG)
+                                 (k == SPP_NET_ACM && !a->plain) || k == SPP_NET_ACTOR_TARG)
                               : k != SPP_NET_ACTOR_TARG;
     SPP_REQUIRE(!used || a->net[k].p, SPP_E_STATE, "network %d parameters not bound", k);
   }
@@ -1003,7 +1013,7 @@ static sppStatus build_packs(sppAgent* a) {
       a->acm.tb2 = T(b2, 32);
       a->acm.tb3 = T(b3, ac);
     }
-  } else {
+  } else if (!a->plain) {
     // ---- BasicAcM (acm/models/basic_acm.py:11-21): t, t1, fc1 [100][2ob], fc2 [50][100],
     //      fc21 [50][2ob], fc3 [ac][50]
     const float* P = a->net[SPP_NET_ACM].p;
@@ -1195,6 +1205,8 @@ static int phase_grid(sppAgent* a, int Bp);
 static int sac_grid(sppAgent* a, int Bp);
 static int sac_critic_grid(sppAgent* a, int Bp);
 static bool sac_team(sppAgent* a, int Bp);
+static bool ddpg_team(sppAgent* a, int Bp);
+static int ddpg_grid(sppAgent* a, int Bp);
 static sppStatus build_dw(sppAgent* a, int set, int B) {
   const int Bp = (int)round_up(B, 32);
   const int ob = a->cfg.ob, aout = a->cfg.aout, ac = a->cfg.ac;
@@ -1232,7 +1244,7 @@ static sppStatus build_dw(sppAgent* a, int set, int B) {
       if (ob <= 32) {  // fc3: fused into k_ddpg_critic_phase (reduce only; its kFuse3)
         J(nullptr, 1, nullptr, 256, nullptr, 0, gw3, gb3);
         jobs.back().fused = 1;
-        jobs.back().nsplit = phase_grid(a, Bp) * kWavesPerWG;
+        jobs.back().nsplit = ddpg_grid(a, Bp) * (ddpg_team(a, Bp) ? kTeamDCritic : kWavesPerWG);
         jobs.back().wsplit = 1;
         fused0 = (int)jobs.size() - 1;
       } else {
@@ -1255,6 +1267,7 @@ static sppStatus build_dw(sppAgent* a, int set, int B) {
       a->w3p_stride = fused0 >= 0 ? jobs[fused0].slab_stride : 0;
       return s;
     } else {
+      SPP_REQUIRE(!a->plain, SPP_E_STATE, "vanilla DDPG has no ACM to regress");
       // BasicAcM regression (acm.py:246-258): fc1, fc2, fc21 (grad of its output = t * dz), fc3;
       // t / t1 come from the per-tile partials (k_finalize_bacm)
       float* G = a->net[SPP_NET_ACM].g;
@@ -1416,6 +1429,15 @@ static int sac_critic_grid(sppAgent* a, int Bp) {
   return sac_team(a, Bp) && 2 * nt <= a->num_cu ? 2 * nt : sac_grid(a, Bp);
 }
 
+// DDPG phases of the vanilla handles: the team kernels (one workgroup per tile, ddpg_team.h) while the tiles
+// fit one per CU; SPP_SAC_TEAM=0 keeps the one-wave kernels at every batch
+static bool ddpg_team(sppAgent* a, int Bp) {
+  return a->ks.dcritic_team && a->ks.dactor_team && a->team_ok && Bp / 32 <= a->num_cu;
+}
+static int ddpg_grid(sppAgent* a, int Bp) {
+  return ddpg_team(a, Bp) ? std::max(1, std::min(Bp / 32, a->num_cu)) : phase_grid(a, Bp);
+}
+
 static sppStatus check_ready(sppAgent* a) {
   SPP_REQUIRE(a->ddpg || (a->alpha_state && a->alpha_f32), SPP_E_STATE, "alpha not bound");
   SPP_REQUIRE(a->cfg.min_max_denormalize ? (a->lo && a->hi) : (a->mean && a->std), SPP_E_STATE,
@@ -1434,10 +1456,14 @@ extern "C" {
 
 sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int device) {
   SPP_REQUIRE(out && cfg, SPP_E_INVALID_ARG, "null arg");
-  SPP_REQUIRE(cfg->algo == SPP_ALGO_SAC_ACM || cfg->algo == SPP_ALGO_DDPG_ACM || cfg->algo == SPP_ALGO_SAC,
+  SPP_REQUIRE(cfg->algo == SPP_ALGO_SAC_ACM || cfg->algo == SPP_ALGO_DDPG_ACM || cfg->algo == SPP_ALGO_SAC ||
+                  cfg->algo == SPP_ALGO_DDPG,
               SPP_E_INVALID_ARG, "unsupported algo %d", cfg->algo);
   SPP_REQUIRE(cfg->algo != SPP_ALGO_SAC || (cfg->acm_critic == 0 && cfg->aout == cfg->ac && cfg->custom_loss == 0.f),
               SPP_E_INVALID_ARG, "vanilla SAC: the actor emits the env action (aout == ac), no ACM critic / loss");
+  SPP_REQUIRE(cfg->algo != SPP_ALGO_DDPG || (cfg->acm_critic == 0 && cfg->aout == cfg->ac && cfg->custom_loss == 0.f),
+              SPP_E_INVALID_ARG, "vanilla DDPG: the actor emits the env action (aout == ac), no ACM critic / loss");
+  SPP_REQUIRE(cfg->algo != SPP_ALGO_DDPG || cfg->mlp_bf16 == 0, SPP_E_INVALID_ARG, "vanilla DDPG: fp32 only");
   SPP_REQUIRE(cfg->max_batch > 0, SPP_E_INVALID_ARG, "max_batch must be > 0");
   KernelSet ks;
   SPP_REQUIRE(find_kset(cfg->algo, cfg->ob, cfg->aout, cfg->ac, cfg->acm_critic != 0, cfg->mlp_bf16 != 0, &ks),
@@ -1457,14 +1483,14 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
   }
   const int ob = cfg->ob, aout = cfg->aout, ac = cfg->ac;
   a->cin = ob + (cfg->acm_critic ? ac : aout);
-  a->ddpg = cfg->algo == SPP_ALGO_DDPG_ACM;
-  a->plain = cfg->algo == SPP_ALGO_SAC;
+  a->ddpg = cfg->algo == SPP_ALGO_DDPG_ACM || cfg->algo == SPP_ALGO_DDPG;
+  a->plain = cfg->algo == SPP_ALGO_SAC || cfg->algo == SPP_ALGO_DDPG;
   const bool dd = a->ddpg;
   a->nsize[SPP_NET_ACTOR] = dd ? ddpg_actor_size(ob, aout) : sac_actor_size(ob, aout);
   a->nsize[SPP_NET_ACTOR_TARG] = dd ? ddpg_actor_size(ob, aout) : 0;
   a->nsize[SPP_NET_CRITIC1] = a->nsize[SPP_NET_CRITIC1_TARG] = critic_size(a->cin);
   a->nsize[SPP_NET_CRITIC2] = a->nsize[SPP_NET_CRITIC2_TARG] = dd ? 0 : critic_size(a->cin);
-  a->nsize[SPP_NET_ACM] = dd ? bacm_size(2 * ob, ac) : acm_size(2 * ob, ac);
+  a->nsize[SPP_NET_ACM] = dd ? (a->plain ? 0 : bacm_size(2 * ob, ac)) : acm_size(2 * ob, ac);
   a->Bmax = cfg->max_batch;
   const int64_t Bp = round_up(cfg->max_batch, 32);
   SPP_REQUIRE((int64_t)Bp * 256 * 4 < ((int64_t)1 << 31), SPP_E_SHAPE, "max_batch %d too large (31-bit buffer offsets)",
@@ -1822,7 +1848,9 @@ sppStatus sppDdpgAcmCriticGrads(sppAgentHandle a, const sppBatch* bt, float* los
               st);
   SacArgs p = make_args(a, B);
   tmark(a, 0, st);
-  hipLaunchKernelGGL(a->ks.dcritic, dim3(phase_grid(a, p.Bp)), dim3(256), 0, st, p, a->bz);
+  const bool team = ddpg_team(a, p.Bp);
+  hipLaunchKernelGGL(team ? a->ks.dcritic_team : a->ks.dcritic, dim3(ddpg_grid(a, p.Bp)),
+                     dim3(team ? 64 * kTeamDCritic : 256), 0, st, p, a->bz);
   tmark(a, 0, st);
   SPP_CHECK_HIP(hipGetLastError());
   tmark(a, 2, st);
@@ -1850,7 +1878,9 @@ sppStatus sppDdpgAcmActorGrads(sppAgentHandle a, float* losses, void* stream) {
   launch_pack(a, a->o_cfwd, (int)a->pj_critic_fwd.size(), st);  // the updated critic
   SacArgs p = make_args(a, B);
   tmark(a, 1, st);
-  hipLaunchKernelGGL(a->ks.dactor, dim3(phase_grid(a, p.Bp)), dim3(256), 0, st, p, a->bz);
+  const bool team = ddpg_team(a, p.Bp);
+  hipLaunchKernelGGL(team ? a->ks.dactor_team : a->ks.dactor, dim3(ddpg_grid(a, p.Bp)),
+                     dim3(team ? 64 * kTeamDActor : 256), 0, st, p, a->bz);
   tmark(a, 1, st);
   SPP_CHECK_HIP(hipGetLastError());
   tmark(a, 2, st);
@@ -1933,6 +1963,7 @@ sppStatus sppSacAcmUpdateStaged(sppAgentHandle a, uint64_t seed, uint64_t counte
 sppStatus sppAcmRegressGrads(sppAgentHandle a, const float* x, const float* y, int B, float* loss, void* stream) {
   SPP_REQUIRE(a && x && y && B > 0 && B <= a->Bmax, SPP_E_INVALID_ARG, "acm step: bad args (B=%d, max %d)", B,
               a->Bmax);
+  SPP_REQUIRE(!(a->ddpg && a->plain), SPP_E_STATE, "vanilla DDPG has no ACM to regress");
   hipStream_t st = S(stream);
   sppStatus s = check_ready(a);
   if (s) return s;
@@ -1974,6 +2005,7 @@ sppStatus sppAcmRegressGrads(sppAgentHandle a, const float* x, const float* y, i
 
 sppStatus sppAcmRegressApply(sppAgentHandle a, void* stream) {
   SPP_REQUIRE(a && a->d_adam.ptr, SPP_E_STATE, "agent not ready");
+  SPP_REQUIRE(!(a->ddpg && a->plain), SPP_E_STATE, "vanilla DDPG has no ACM to regress");
   a->steps[3] += 1;
   launch_adam(a, 3, 1, a->net[SPP_NET_ACM].n, a->steps[3], a->cfg.acm_lr, 0.f, S(stream));
   SPP_CHECK_HIP(hipGetLastError());
@@ -2170,7 +2202,9 @@ sppStatus sppPolicyAct(sppAgentHandle a, const float* obs, int E, const float* e
   SacArgs p = make_args(a, 32);
   ActArgs g{E, mode, denorm_out, act_noise, obs, eps, noise, target_out, env_out, a->plain ? 1 : 0};
   const int grid = std::max(1, std::min(cdiv(cdiv(E, 32), kWavesPerWG), a->num_cu));
-  if (a->ddpg)
+  if (a->ddpg && a->plain && a->ks.dact_team && a->team_ok && cdiv(E, 32) <= a->num_cu)  // one tile per CU
+    hipLaunchKernelGGL(a->ks.dact_team, dim3(cdiv(E, 32)), dim3(64 * kTeamDAct), 0, st, p, g, a->bz);
+  else if (a->ddpg)
     hipLaunchKernelGGL(a->ks.dact, dim3(grid), dim3(256), 0, st, p, g, a->bz);
   else if (a->plain && a->ks.act_team && a->team_ok && cdiv(E, 32) <= a->num_cu)  // one tile per CU (sac_team.h)
     hipLaunchKernelGGL(a->ks.act_team, dim3(cdiv(E, 32)), dim3(64 * kTeamCritic), 0, st, p, g);

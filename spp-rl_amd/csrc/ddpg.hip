@@ -456,6 +456,9 @@ __global__ __launch_bounds__(256, 1) void k_ddpg_actor_phase(SacArgs p, BAcmScra
 // DDPG_AcM.noise_action (ddpg_acm.py:40-50) + process_action (off_policy.py:89-106):
 // mode 1: a = clip(tanh(fc3)*lim + act_noise*lim*noise, +-1.1 lim); mode 2: deterministic;
 // mode 0 random: a = lim * eps.  a_d = denormalize(a) if denorm_out; env action = ACM(s, a_d).
+// Plain handles (vanilla DDPG, a.plain): DDPG.noise_action / initial_act / process_action (ddpg.py:171-180,
+// 371-383): mode 0 passes the caller's sample through, mode 1 is clip(tanh(fc3)*lim + act_noise*noise, +-lim),
+// no denormalisation, no BasicAcM: env_out = target_out.
 template <class C>
 __global__ __launch_bounds__(256, 1) void k_ddpg_policy_act(SacArgs p, ActArgs a, BAcmScratch z) {
   __shared__ float smem[kWavesPerWG * kLdsPerWave];
@@ -465,6 +468,8 @@ __global__ __launch_bounds__(256, 1) void k_ddpg_policy_act(SacArgs p, ActArgs a
   float* big = smem + w * kLdsPerWave;
   float* small = big + kSmallRow * 32;
   const int ntiles = (a.E + 31) / 32;
+  // the plain form exists only where the actor output is the env action (the SPP shapes compile as before)
+  const bool plain = !C::ACMC && C::AOUT == C::AC && a.plain;
   for (int tile = blockIdx.x * kWavesPerWG + w; tile < ntiles; tile += gridDim.x * kWavesPerWG) {
     const int e = tile * 32 + (lane & 31);
     const bool valid = e < a.E;
@@ -485,18 +490,26 @@ __global__ __launch_bounds__(256, 1) void k_ddpg_policy_act(SacArgs p, ActArgs a
         if (j < C::AOUT) {
           const float lim = actor_lim<true>(p, L.tbl, j);
           float act;
-          if (a.mode == 0) {
+          if (plain && a.mode == 0) {
+            act = valid ? a.eps[er * C::AOUT + j] : 0.f;  // action_space.sample() drawn by the caller
+          } else if (plain) {
+            act = fmul_rn(tanhf(u[ib][q]), lim);
+            if (a.mode == 1 && a.noise) act = fadd_rn(act, a.act_noise * (valid ? a.noise[er * C::AOUT + j] : 0.f));
+            act = fminf(fmaxf(act, -lim), lim);
+          } else if (a.mode == 0) {
             act = valid ? lim * a.eps[er * C::AOUT + j] : 0.f;
           } else {
             act = fmul_rn(tanhf(u[ib][q]), lim);
             if (a.mode == 1 && a.noise) act += fmul_rn(a.act_noise * (valid ? a.noise[er * C::AOUT + j] : 0.f), lim);
             act = fminf(fmaxf(act, -1.1f * lim), 1.1f * lim);
           }
-          if (a.denorm_out) act = denorm<true>(p, L.tbl, j, act);
+          if (a.denorm_out && !plain) act = denorm<true>(p, L.tbl, j, act);
           L.bl[ur * 32] = act;
           if (valid) a.target_out[er * C::AOUT + j] = act;
+          if (valid && plain) a.env_out[er * C::AOUT + j] = act;  // process_action: identity (AOUT == AC)
         }
       }
+    if (plain) continue;
     f32x16 xin[C::NB_ACMIN];
     load_cat_gl<C::NB_OB, C::NB_AOUT>(xin, a.obs, a.E * C::OB * 4, C::OB, L.ld4, L.vo, big, C::AOUT);
     bacm_forward<C, false>(p, xin, L, z);

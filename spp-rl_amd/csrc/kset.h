@@ -6,6 +6,7 @@
 #include "sac_bf.h"
 #include "ddpg.hip"
 #include "sac_team.h"
+#include "ddpg_team.h"
 
 namespace spp {
 
@@ -25,6 +26,10 @@ struct KernelSet {
   void (*critic_team)(SacArgs);
   void (*actor_team)(SacArgs, AcmScratch);
   void (*act_team)(SacArgs, ActArgs);  // plain handles' rollout action
+  // small-batch (team) forms of the DDPG phases and rollout action (ddpg_team.h): vanilla DDPG handles
+  void (*dcritic_team)(SacArgs, BAcmScratch);
+  void (*dactor_team)(SacArgs, BAcmScratch);
+  void (*dact_team)(SacArgs, ActArgs, BAcmScratch);
 };
 
 template <int OB, int AOUT, int AC, bool ACMC, bool BF = false>
@@ -60,5 +65,6 @@ bool kset_ddpg(int ob, int aout, int ac, bool acmc, KernelSet* ks);          // 
 bool kset_ddpg_ant(int ob, int aout, int ac, bool acmc, KernelSet* ks);      // ks_ddpg_ant.hip
 bool kset_sac_bf16(int ob, int aout, int ac, bool acmc, KernelSet* ks);      // ks_sac_bf16.hip
 bool kset_sac_vanilla(int ob, int aout, int ac, bool acmc, KernelSet* ks);   // ks_sac_vanilla.hip
+bool kset_ddpg_vanilla(int ob, int aout, int ac, bool acmc, KernelSet* ks);  // ks_ddpg_vanilla.hip
 
 }  // namespace spp

@@ -160,9 +160,10 @@ __device__ __forceinline__ void dense_team(const float4* __restrict__ Wf, int ob
 }
 
 // Actor trunk (sac.hip actor_trunk), team form: h1 / h2 split by blocks (masks of the wave's own blocks only),
-// heads (one block, split by input blocks) written to rows [0, 2*AOUT) by wave 0.
+// heads (one block, split by input blocks) written to rows [0, NHR) by wave 0: SAC's (mu | log-std), NHR =
+// 2*AOUT; DDPG's fc3 pre-activation, NHR = AOUT (ddpg_team.h).
 // Returns with the heads in the image, team-synchronised.
-template <class C, bool ST, int TW>
+template <class C, bool ST, int TW, int NHR = 2 * C::AOUT>
 __device__ __forceinline__ void actor_trunk_team(const ActorDev& A, const float* X, int xbytes, const Lane& L,
                                                  int w, float* H1g, float* H2g, float (*part)[16][64],
                                                  uint32_t& m1, uint32_t& m2) {
@@ -208,7 +209,7 @@ __device__ __forceinline__ void actor_trunk_team(const ActorDev& A, const float*
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const int ur = ru(q);
-      if (ur + L.h4 < 2 * C::AOUT) L.bl[ur * 32] = hd[q];
+      if (ur + L.h4 < NHR) L.bl[ur * 32] = hd[q];
     }
   }
   team_sync();

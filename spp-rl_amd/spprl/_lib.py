@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("SPPRL_LIB") or os.path.join(HERE, "libspprl.so")
 
 (SPP_NET_ACTOR, SPP_NET_CRITIC1, SPP_NET_CRITIC2, SPP_NET_CRITIC1_TARG, SPP_NET_CRITIC2_TARG, SPP_NET_ACM,
  SPP_NET_ACTOR_TARG) = range(7)
-SPP_ALGO_SAC_ACM, SPP_ALGO_DDPG_ACM, SPP_ALGO_SAC = 1, 2, 3
+SPP_ALGO_SAC_ACM, SPP_ALGO_DDPG_ACM, SPP_ALGO_SAC, SPP_ALGO_DDPG = 1, 2, 3, 4
 SPP_BUCKET_CRITIC, SPP_BUCKET_ACTOR, SPP_BUCKET_ACM, SPP_BUCKET_ALL = range(4)
 SPP_COMM_ID_BYTES = 128
 SPP_DP1_REUSE_BRACKET = 0x100  # sppReplayObsStatsDP1 phase flag (spprl.h)

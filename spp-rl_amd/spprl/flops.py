@@ -31,19 +31,20 @@ def sac_macs(ob, ac, aout=None, acm_critic=True, with_acm=True):
                 act=act, update=critic_phase + actor_phase + dw)
 
 
-def ddpg_macs(ob, ac, aout=None, acm_critic=True):
-    """DDPG_AcM with BasicAcM (ddpg_acm.py:100-201, train/spp_ddpg_hcheetah.py)."""
+def ddpg_macs(ob, ac, aout=None, acm_critic=True, with_acm=True):
+    """DDPG_AcM with BasicAcM (ddpg_acm.py:100-201, train/spp_ddpg_hcheetah.py).  with_acm=False: vanilla DDPG
+    (algorithms/ddpg/ddpg.py:239-327; pass aout=ac, acm_critic=False)."""
     aout = ob if aout is None else aout
     ca = ac if acm_critic else aout
     A = ob * H + H * H + H * aout                 # actor forward
-    M = 2 * ob * 100 + 100 * 50 + 2 * ob * 50 + 50 * ac   # BasicAcM forward (fc1, fc2, fc21 skip, fc3)
+    M = (2 * ob * 100 + 100 * 50 + 2 * ob * 50 + 50 * ac) if with_acm else 0  # BasicAcM forward (fc1, fc2, fc21 skip, fc3)
     C = (ob + ca) * H + H * H + H
     critic_phase = A + M + C + C + (H + H * H)    # target actor, ACM, target critic; critic fwd + bwd
     actor_phase = (A + M + C + (H + H * H + ca * H)          # actor fwd, ACM, critic fwd; dQ/da
-                   + (ac * 50 + 50 * 100 + 100 * aout + 50 * aout)  # through BasicAcM to the actor output
+                   + ((ac * 50 + 50 * 100 + 100 * aout + 50 * aout) if with_acm else 0)  # through BasicAcM to the actor output
                    + (aout * H + H * H))                      # actor head + layer-2 input gradients
     dw = C + A
-    acm_reg = M + M + (ac * 50 + 50 * 100)
+    acm_reg = (M + M + (ac * 50 + 50 * 100)) if with_acm else 0
     act = A + M
     return dict(A=A, M=M, C=C, critic_phase=critic_phase, actor_phase=actor_phase, dw=dw, acm_reg=acm_reg,
                 act=act, update=critic_phase + actor_phase + dw)
