@@ -471,7 +471,8 @@ sppStatus sppOnpActorApply(sppOnPolicyHandle h, void* stream);
  * LDS for the launch; bs > 64 spreads each step over ceil(bs / 64) co-resident workgroups whose gradients
  * are summed in a fixed order (deterministic).  Data-parallel PPO_AcM runs it on every rank over the all-gathered
  * union batch (replicated, no per-step exchange; sppOnpActorGrads / Apply + an all-reduce remain for callers
- * that shard the minibatch).  Instantiated for (ob, aout) = (17, 17), (11, 11). */
+ * that shard the minibatch).  Instantiated for (ob, aout) = (17, 17), (11, 11) (SPP-PPO: aout = ob, next_obs
+ * [n][ob]) and (17, 6), (11, 3) (vanilla PPO: aout = ac, next_obs NULL). */
 sppStatus sppOnpActorEpoch(sppOnPolicyHandle h, const float* x, const float* act, const float* lp_old,
                            const float* adv, const float* next_obs, const int64_t* idx, int nrows, int bs,
                            float* out4, void* stream);
@@ -513,6 +514,26 @@ sppStatus sppOnpReserveWorkgroups(sppOnPolicyHandle h, int n);
  * deterministic mu), logp = Independent(Normal).log_prob(a). */
 sppStatus sppOnpAct(sppOnPolicyHandle h, const float* x, int N, const float* eps, float* act_out, float* logp_out,
                     void* stream);
+/* One rollout step of vanilla A2C / PPO (a2c.py:164-167) in ONE launch, for few env rows (one 64-lane workgroup
+ * per row; built for E up to a few hundred, callers with more rows use sppObsNormalize + sppRandNormal +
+ * sppOnpAct): obs [E][ob] RAW observations are standardised and clipped with mean / std [ob] (utils
+ * standardize_and_clip; both NULL: passed through), the policy's standard-normal draws are taken from
+ * (seed, offset) -- bit for bit what sppRandNormal(out, E * aout, seed, offset) writes -- or, with
+ * deterministic != 0, the mean is returned; the actor runs from the canonical parameters bound by sppOnpBindNet
+ * (no packed images: always current with them).  act_out [E][aout], logp_out [E] (NULL: skipped) as sppOnpAct;
+ * norm_obs_out [E][ob] and noise_out [E][aout] (zeros when deterministic) are optional (NULL). */
+sppStatus sppOnpRolloutAct(sppOnPolicyHandle h, const float* obs, int E, const float* mean, const float* std,
+                           uint64_t seed, uint64_t offset, int deterministic, float* act_out, float* logp_out,
+                           float* norm_obs_out, float* noise_out, void* stream);
+/* Memory.update_obs_mean_std (rltoolkit/buffer/memory.py:283-302) in one launch: column mean and unbiased
+ * (ddof = 1) std, accumulated in fp64, over the n_start + n_next rows of start_obs (each rollout's first
+ * observation) and next_obs (every frame's next observation), blended in place as
+ * mean = (1 - alpha) new + alpha mean (std alike); max_obs / min_obs = the exact 99th / 1st np.percentile (linear
+ * interpolation, cast to fp32) of the n_obs rows of obs per column -- a radix select, no sort -- assigned when
+ * have_minmax == 0, else max / min with the running pair.  Plain row-major [rows][ob] device arrays. */
+sppStatus sppOnpObsStats(const float* start_obs, int64_t n_start, const float* next_obs, int64_t n_next,
+                         const float* obs, int64_t n_obs, int ob, double alpha, float* mean, float* std,
+                         float* max_obs, float* min_obs, int have_minmax, void* stream);
 
 /* Debug / layout check: y = act(x W^T + b) through the MFMA register-tile path.
  * x [B][K], W [N][K], b [N], y [B][N]; act 0 none, 1 relu, 2 tanh. */

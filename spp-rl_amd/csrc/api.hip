@@ -43,6 +43,7 @@
 #endif
 #endif
 #include "onp.hip"
+#include "onp_rollout.hip"
 #include "sgd.hip"
 #include "sgd_mlp.hip"
 
@@ -2264,16 +2265,18 @@ struct OnpKernels {
   void (*critic)(OnpArgs);
   void (*actor)(OnpArgs);
   void (*act)(OnpArgs);
+  void (*rollout)(OnpRolloutArgs);
 };
 template <int OB, int AOUT>
 OnpKernels make_onp() {
   using C = OCfg<OB, AOUT>;
-  return {k_onp_value<C>, k_onp_critic_grad<C>, k_onp_actor_grad<C>, k_onp_act<C>};
+  return {k_onp_value<C>, k_onp_critic_grad<C>, k_onp_actor_grad<C>, k_onp_act<C>, k_onp_rollout_act<OB, AOUT>};
 }
 static bool find_onp(int ob, int aout, OnpKernels* k) {
   if (ob == 17 && aout == 17) { *k = make_onp<17, 17>(); return true; }  // SPP-PPO HalfCheetah
   if (ob == 11 && aout == 11) { *k = make_onp<11, 11>(); return true; }  // Hopper
   if (ob == 17 && aout == 6) { *k = make_onp<17, 6>(); return true; }    // vanilla PPO HalfCheetah
+  if (ob == 11 && aout == 3) { *k = make_onp<11, 3>(); return true; }    // vanilla PPO Hopper
   if (ob == 3 && aout == 1) { *k = make_onp<3, 1>(); return true; }      // Pendulum (tests)
   return false;
 }
@@ -2583,6 +2586,8 @@ static int onp_epoch_max_wg(sppOnPolicy* o) {
   int n = 0;
   if (ob == 17 && aout == 17) n = mlp_sgd_max_wg<17, 64, 17, 1>(o->num_cu);
   else if (ob == 11 && aout == 11) n = mlp_sgd_max_wg<11, 64, 11, 1>(o->num_cu);
+  else if (ob == 17 && aout == 6) n = mlp_sgd_max_wg<17, 64, 6, 1>(o->num_cu);  // vanilla PPO: aout = ac
+  else if (ob == 11 && aout == 3) n = mlp_sgd_max_wg<11, 64, 3, 1>(o->num_cu);
   o->sgd_max_wg = n;
   return n;
 }
@@ -2628,11 +2633,14 @@ sppStatus sppOnpActorEpoch(sppOnPolicyHandle o, const float* x, const float* act
     g.err = o->sgd_sync.ptr + 1;
   }
   const bool mw = nwg > 1;
-#define SPP_EPOCH_LAUNCH(OB_)                                                                          \
-  if (mw) hipLaunchKernelGGL((k_mlp_sgd<OB_, 64, OB_, 1, true>), dim3(nwg), dim3(kMlTH), 0, st, g);     \
-  else hipLaunchKernelGGL((k_mlp_sgd<OB_, 64, OB_, 1, false>), dim3(1), dim3(kMlTH), 0, st, g)
-  if (o->cfg.ob == 17) SPP_EPOCH_LAUNCH(17);
-  else SPP_EPOCH_LAUNCH(11);
+#define SPP_EPOCH_LAUNCH(OB_, OUT_)                                                                     \
+  if (mw) hipLaunchKernelGGL((k_mlp_sgd<OB_, 64, OUT_, 1, true>), dim3(nwg), dim3(kMlTH), 0, st, g);     \
+  else hipLaunchKernelGGL((k_mlp_sgd<OB_, 64, OUT_, 1, false>), dim3(1), dim3(kMlTH), 0, st, g)
+  // (maxwg > 0 above: one of onp_epoch_max_wg's four pairs)
+  if (o->cfg.ob == 17 && o->cfg.aout == 17) SPP_EPOCH_LAUNCH(17, 17);
+  else if (o->cfg.ob == 11 && o->cfg.aout == 11) SPP_EPOCH_LAUNCH(11, 11);
+  else if (o->cfg.ob == 17) SPP_EPOCH_LAUNCH(17, 6);
+  else SPP_EPOCH_LAUNCH(11, 3);
 #undef SPP_EPOCH_LAUNCH
   o->steps[0] += nsteps;
   SPP_CHECK_HIP(hipGetLastError());
@@ -2746,6 +2754,40 @@ sppStatus sppOnpAct(sppOnPolicyHandle o, const float* x, int N, const float* eps
   OnpArgs p = onp_args(o, N);
   p.X = x; p.EPS = eps; p.ACT_OUT = act_out; p.LP_OUT = logp_out;
   hipLaunchKernelGGL(o->ks.act, dim3(onp_grid(o, N)), dim3(256), 0, st, p);
+  SPP_CHECK_HIP(hipGetLastError());
+  return SPP_OK;
+}
+
+sppStatus sppOnpRolloutAct(sppOnPolicyHandle o, const float* obs, int E, const float* mean, const float* std,
+                           uint64_t seed, uint64_t offset, int deterministic, float* act_out, float* logp_out,
+                           float* norm_obs_out, float* noise_out, void* stream) {
+  SPP_REQUIRE(o && obs && act_out && E > 0, SPP_E_INVALID_ARG, "rollout act: bad args");
+  SPP_REQUIRE((mean == nullptr) == (std == nullptr), SPP_E_INVALID_ARG, "rollout act: mean and std, or neither");
+  SPP_REQUIRE(o->net[0].p && o->lim.ptr, SPP_E_STATE, "rollout act: actor not bound / limits not set");
+  OnpRolloutArgs p{};
+  p.obs = obs; p.mean = mean; p.std = std; p.P = o->net[0].p; p.lim = o->lim.ptr;
+  p.seed = seed; p.offset = offset; p.E = E; p.deterministic = deterministic;
+  p.act = act_out; p.lp = logp_out; p.xn = norm_obs_out; p.noise = noise_out;
+  hipLaunchKernelGGL(o->ks.rollout, dim3(E), dim3(64), 0, S(stream), p);
+  SPP_CHECK_HIP(hipGetLastError());
+  return SPP_OK;
+}
+
+sppStatus sppOnpObsStats(const float* start_obs, int64_t n_start, const float* next_obs, int64_t n_next,
+                         const float* obs, int64_t n_obs, int ob, double alpha, float* mean, float* std,
+                         float* max_obs, float* min_obs, int have_minmax, void* stream) {
+  SPP_REQUIRE(ob > 0 && n_start >= 0 && n_next >= 0 && n_obs >= 0 && (start_obs || n_start == 0) &&
+                  (next_obs || n_next == 0) && (obs || n_obs == 0),
+              SPP_E_INVALID_ARG, "obs stats: bad rows");
+  SPP_REQUIRE(mean && std && max_obs && min_obs && alpha >= 0.0 && alpha <= 1.0, SPP_E_INVALID_ARG,
+              "obs stats: null statistics or alpha outside [0, 1]");
+  if (n_start + n_next == 0 && n_obs == 0) return SPP_OK;
+  OnpStatsArgs a{};
+  a.start = start_obs; a.next = next_obs; a.obs = obs;
+  a.n_start = n_start; a.n_next = n_next; a.n_obs = n_obs;
+  a.ob = ob; a.have_minmax = have_minmax; a.alpha = alpha;
+  a.mean = mean; a.std = std; a.max_obs = max_obs; a.min_obs = min_obs;
+  hipLaunchKernelGGL(k_onp_obs_stats, dim3(ob), dim3(256), 0, S(stream), a);
   SPP_CHECK_HIP(hipGetLastError());
   return SPP_OK;
 }

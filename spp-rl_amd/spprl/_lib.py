@@ -132,6 +132,12 @@ _SIGS = {
                                  c_void_p]),
     "sppOnpActorApply": (c_int, [c_void_p, c_void_p]),
     "sppOnpAct": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # h, raw obs, E, mean, std, seed, offset, deterministic, act, logp, norm obs, noise, stream
+    "sppOnpRolloutAct": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_uint64, c_uint64, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    # start obs, rows, next obs, rows, obs, rows, ob, alpha, mean, std, max, min, have_minmax, stream
+    "sppOnpObsStats": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, ctypes.c_double,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "sppGaeScan": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_double,
                            ctypes.c_double,
                             c_int, c_void_p, c_void_p, c_void_p]),

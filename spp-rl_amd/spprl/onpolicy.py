@@ -236,6 +236,8 @@ class OnPolicyNets:
         s = sums.cpu().numpy().astype(np.float64)
         d = float(i + 1)
         self.loss.update(actor=s[0] / d, entropy=s[3] / d, kl=kl)
+        # the undivided sums over every minibatch step: vanilla PPO logs these (ppo.py:185-187, no division)
+        self.loss_sums = {"actor": s[0], "entropy": s[3], "sum": s[0] - self.entropy_coef * s[3]}
         if nxt is not None:  # PPO_AcM: dist = mse(actions, next_obs) (data only: no gradient), and
             # policy = actor - entropy_coef * entropy + custom_loss * dist per minibatch (on_policy.py:188-207)
             self.loss.update(dist=s[2] / d, policy=(s[0] - self.entropy_coef * s[3] + self.custom_loss * s[2]) / d)
@@ -304,3 +306,49 @@ class OnPolicyNets:
         call("sppOnpAct", self._h, ptr(x), N, ptr(e), ptr(a), ptr(lp), stream_handle())
         self._keep = (x, e)
         return a, lp
+
+    def rollout_act(self, obs, mean, std, seed, offset, deterministic=False, fused=None, want_noise=False):
+        """One rollout step of vanilla A2C / PPO (a2c.py:165-166) on RAW observations [E][ob]: standardize_and_clip
+        with mean / std (both None: passed through), the draws of sppRandNormal(E * aout, seed, offset), Actor.act.
+        Returns (action, log_prob, normalised obs, noise or None).  Up to FUSED_ACT_MAX_ROWS rows take the one-launch
+        kernel (sppOnpRolloutAct, from the canonical parameters); more rows, or SPP_PPO_FUSED_ACT=0, the sequence
+        sppObsNormalize + sppRandNormal + sppOnpAct -- the same draws, bit for bit."""
+        import os
+
+        x = self._dev(obs)
+        E = x.shape[0]
+        if fused is None:
+            fused = E <= FUSED_ACT_MAX_ROWS and os.environ.get("SPP_PPO_FUSED_ACT", "1") != "0"
+        a = torch.empty(E, self.aout, device=self.device)
+        lp = torch.empty(E, device=self.device)
+        if fused:
+            xn = torch.empty_like(x)
+            eps = torch.empty(E, self.aout, device=self.device) if want_noise else None
+            call("sppOnpRolloutAct", self._h, ptr(x), E, ptr(mean), ptr(std), int(seed), int(offset),
+                 int(bool(deterministic)), ptr(a), ptr(lp), ptr(xn), ptr(eps), stream_handle())
+            self._keep = (x, mean, std)
+            return a, lp, xn, eps
+        if mean is None:
+            xn = x.clone()  # the caller keeps it: never alias the env's double-buffered obs
+        else:
+            xn = torch.empty_like(x)
+            call("sppObsNormalize", ptr(x), E, self.ob, None, None, ptr(mean), ptr(std), 0, 0, ptr(xn), stream_handle())
+        eps = None
+        if not deterministic:
+            eps = torch.empty(E, self.aout, device=self.device)
+            call("sppRandNormal", ptr(eps), eps.numel(), int(seed), int(offset), stream_handle())
+        call("sppOnpAct", self._h, ptr(xn), E, ptr(eps), ptr(a), ptr(lp), stream_handle())
+        self._keep = (x, xn, eps, mean, std)
+        return a, lp, xn, (eps if want_noise else None)
+
+
+FUSED_ACT_MAX_ROWS = 256  # one 64-lane workgroup per row: up to one row per CU of the device
+
+
+def obs_stats(start_obs, next_obs, obs, alpha, mean, std, max_obs, min_obs, have_minmax):
+    """Memory.update_obs_mean_std (memory.py:283-302) on device rows, in place (sppOnpObsStats)."""
+    ob = mean.numel()
+    s, n, o = (t.reshape(-1, ob).contiguous() for t in (start_obs, next_obs, obs))
+    call("sppOnpObsStats", ptr(s), s.shape[0], ptr(n), n.shape[0], ptr(o), o.shape[0], ob, float(alpha), ptr(mean),
+         ptr(std), ptr(max_obs), ptr(min_obs), int(bool(have_minmax)), stream_handle())
+    return s, n, o  # (alive until the stream has passed the launch: the caller keeps them)
