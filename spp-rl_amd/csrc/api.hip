@@ -879,6 +879,9 @@ struct sppAgent {
   float *aux = nullptr;  // [4] alpha grad operand (all-reduced in DP)
   float* GAD = nullptr;       // wide-head actor phase: d a_d hand-over [aout][Bp]
   uint64_t* MASK = nullptr;   // and the trunk's ReLU masks [tile][4][64]
+  // min-critic split of the one-wave actor phase (sac.hip: AcmScratch; SPP_MINQ_SPLIT=0: the one-kernel phase, A/B)
+  bool minq_split = false;
+  AcmScratch mq{};  // its hand-over buffers (SEL ... DCA)
   // ACM regression scratch
   float *RX = nullptr, *RZ1 = nullptr, *RZ2 = nullptr, *RP1 = nullptr, *RP2 = nullptr, *RP3 = nullptr;
   // weight-gradient job sets: [0] SAC (critic phase, actor phase), [1] ACM regression
@@ -1481,6 +1484,8 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
   {
     const char* t = getenv("SPP_SAC_TEAM");
     a->team_ok = !(t && t[0] == '0');
+    const char* m = getenv("SPP_MINQ_SPLIT");
+    a->minq_split = ks.actor_fwd && ks.actor_minq && ks.actor_bwd && !(m && m[0] == '0');
   }
   const int ob = cfg->ob, aout = cfg->aout, ac = cfg->ac;
   a->cin = ob + (cfg->acm_critic ? ac : aout);
@@ -1516,6 +1521,13 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
   const int64_t oRS21 = dd ? take(64) : 0, oRPZ21 = dd ? take(64) : 0;
   // wide-head actor phase hand-over: d a_d [aout][Bp], ReLU masks (4 x u64 per lane = 16 floats per sample)
   const int64_t oGAD = take(aout), oMASK = take(16);
+  // min-critic split hand-over (AcmScratch): selectors (1 B per sample), both critics' masks (128 B per sample),
+  // per-tile counts | list offsets | list lengths (ntiles + 2 ntiles + 2 words <= Bp), the two lists, and
+  // d q_i / d (critic action input) [CA][Bp] per critic
+  const bool mq = a->minq_split;
+  const int64_t ca = a->cin - ob;
+  const int64_t oSEL = mq ? take(1) : 0, oCM = mq ? take(32) : 0, oCNT = mq ? take(1) : 0, oLIST = mq ? take(2) : 0,
+                oDCA = mq ? take(2 * ca) : 0;
   const int64_t oPart = total;
   total += ntiles * kBParts + 64;
   const int64_t oAux = total;
@@ -1536,6 +1548,19 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
   a->Z1 = b + oZ1; a->Z2 = b + oZ2; a->T3 = b + oT3;
   a->GAD = b + oGAD;
   a->MASK = reinterpret_cast<uint64_t*>(b + oMASK);
+  if (mq) {
+    AcmScratch& q = a->mq;
+    q.Z1 = a->Z1; q.Z2 = a->Z2; q.T3 = a->T3; q.GAD = a->GAD; q.MASK = a->MASK;
+    q.SEL = reinterpret_cast<uint8_t*>(b + oSEL);
+    q.CM = reinterpret_cast<uint64_t*>(b + oCM);
+    q.CNT = reinterpret_cast<uint32_t*>(b + oCNT);
+    q.OFF = q.CNT + ntiles;
+    q.NG = reinterpret_cast<int*>(q.OFF + 2 * ntiles);
+    q.LIST[0] = reinterpret_cast<int*>(b + oLIST);
+    q.LIST[1] = q.LIST[0] + Bp;
+    q.DCA[0] = b + oDCA;
+    q.DCA[1] = q.DCA[0] + ca * Bp;
+  }
   a->RX = b + oRX; a->RZ1 = b + oRZ1; a->RZ2 = b + oRZ2; a->RP1 = b + oRP1; a->RP2 = b + oRP2; a->RP3 = b + oRP3;
   if (dd) {
     a->bz = BAcmScratch{a->Z1, a->Z2, a->T3};
@@ -1703,8 +1728,20 @@ static sppStatus actor_grads(sppAgentHandle a, float* losses, hipStream_t st) {
   const int grid = sac_grid(a, p.Bp);
   tmark(a, 1, st);
   const bool team = sac_team(a, p.Bp);
-  hipLaunchKernelGGL(team ? a->ks.actor_team : a->ks.actor, dim3(grid), dim3(team ? 64 * kTeamActor : 256), 0, st, p, z);
-  if (a->ks.actor_heads) hipLaunchKernelGGL(a->ks.actor_heads, dim3(grid), dim3(256), 0, st, p, z);
+  if (!team && a->minq_split) {
+    // min-critic split: forward to q = min(Q1, Q2); the two lists of samples by chosen critic; that critic's
+    // backward over the regrouped samples; everything behind it in the original order (sac.hip)
+    z = a->mq;
+    hipLaunchKernelGGL(a->ks.actor_fwd, dim3(grid), dim3(256), 0, st, p, z);
+    hipLaunchKernelGGL(k_minq_scan, dim3(1), dim3(kMinqScanThreads), 0, st, (const uint32_t*)z.CNT, z.OFF, z.NG, p.Bp / 32);
+    hipLaunchKernelGGL(k_minq_scatter, dim3(cdiv(p.Bp, 256)), dim3(256), 0, st, (const uint8_t*)z.SEL,
+                       (const uint32_t*)z.OFF, z.LIST[0], z.LIST[1], p.Bp);
+    hipLaunchKernelGGL(a->ks.actor_minq, dim3(grid), dim3(256), 0, st, p, z);
+    hipLaunchKernelGGL(a->ks.actor_bwd, dim3(grid), dim3(256), 0, st, p, z);
+  } else {
+    hipLaunchKernelGGL(team ? a->ks.actor_team : a->ks.actor, dim3(grid), dim3(team ? 64 * kTeamActor : 256), 0, st, p, z);
+    if (a->ks.actor_heads) hipLaunchKernelGGL(a->ks.actor_heads, dim3(grid), dim3(256), 0, st, p, z);
+  }
   tmark(a, 1, st);
   SPP_CHECK_HIP(hipGetLastError());
   tmark(a, 2, st);

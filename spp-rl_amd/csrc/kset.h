@@ -30,6 +30,11 @@ struct KernelSet {
   void (*dcritic_team)(SacArgs, BAcmScratch);
   void (*dactor_team)(SacArgs, BAcmScratch);
   void (*dact_team)(SacArgs, ActArgs, BAcmScratch);
+  // min-critic split of the one-wave SAC actor phase (fp32 sets; sac.hip): forward to q = min(Q1, Q2), the
+  // chosen critics' backward over the regrouped samples, and everything behind it; null where there is none
+  void (*actor_fwd)(SacArgs, AcmScratch);
+  void (*actor_minq)(SacArgs, AcmScratch);
+  void (*actor_bwd)(SacArgs, AcmScratch);
 };
 
 template <int OB, int AOUT, int AC, bool ACMC, bool BF = false>
@@ -41,8 +46,14 @@ KernelSet make_kset() {
 #if SPP_BF16_TWO_TILES
   if constexpr (C::BF && C::ACMC && !C::F3) critic = k_sac_critic_phase2<C>;  // two tiles per wave (sac_bf.h)
 #endif
-  return {critic, k_sac_actor_phase<C>, heads, k_policy_act<C>, k_acm_regress<C>,
-          nullptr, nullptr, nullptr, nullptr};
+  KernelSet ks{critic, k_sac_actor_phase<C>, heads, k_policy_act<C>, k_acm_regress<C>,
+               nullptr, nullptr, nullptr, nullptr};
+  if constexpr (!C::BF) {
+    ks.actor_fwd = k_sac_actor_phase<C, true>;
+    ks.actor_minq = k_sac_minq_backward<C>;
+    ks.actor_bwd = k_sac_actor_heads<C, true>;
+  }
+  return ks;
 }
 template <int OB, int AOUT, int AC, bool ACMC>
 KernelSet make_dkset() {

@@ -704,9 +704,190 @@ struct AcmScratch {
   // d loss / d a_d [AOUT][Bp] (GAD) and the trunk's ReLU masks [tile][4][64 lanes] (MASK)
   float* GAD;
   uint64_t* MASK;
+  // min-critic split (SPLIT kernels below): the forward kernel hands the compacted critic backward
+  //   SEL  [Bp]            per sample: bit 0 = critic 1 takes the gradient, bit 1 = critic 2 (3 = exact tie,
+  //                        0 = dead: b >= B, or no order between q1 and q2)
+  //   CM   [2][Bp][2][4]   each critic's fc1 / fc2 ReLU masks, 32 B per (sample, lane half)
+  //   CNT  [ntiles]        samples of the tile in list 1 | in list 2 << 16 (wave ballots)
+  // k_minq_scan / k_minq_scatter turn the counts into
+  //   OFF  [ntiles][2]     list positions of the tile's first entries (exclusive prefix sums)
+  //   NG   [2]             lengths of the two lists
+  //   LIST [2][Bp]         sample indices, ascending
+  // and the compacted backward stores d q_i / d (critic action input) at the sample's own column of
+  //   DCA  [2][CA][Bp]
+  uint8_t* SEL;
+  uint64_t* CM;
+  uint32_t *CNT, *OFF;
+  int* NG;
+  int* LIST[2];
+  float* DCA[2];
 };
 
-template <class C>
+// d a_d through the frozen ACM (basic_model.py:118-126 backward): dca -> image rows [0, AOUT).
+// PRE: every scratch value of the three layers is requested up front: buffer loads cannot be
+// moved across the epilogues' LDS stores (no alias proof), so loads issued inside an
+// epilogue run as one round trip each.  (Kernels whose registers are taken keep the per-element loads.)
+template <class C, bool PRE>
+__device__ __forceinline__ void acm_backward(const SacArgs& p, const AcmScratch& z, const Lane& L, float* small,
+                                             const f32x16 (&dca)[C::NB_CA]) {
+  constexpr bool kPre = PRE;
+  float t3v[16], limv[16], z2v[16], z1v[2][16];
+  const rsrc_t t3r = rsrc_n(z.T3, C::AC * L.ld4);  // rows >= AC read 0
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int u = ru(q) + L.h4;
+    t3v[q] = fm_ldb(t3r, ru(q), L.ld4, L.vo);
+    limv[q] = acm_lim<true>(p, L.tbl, u < C::AC ? u : 0);
+  }
+  if constexpr (kPre) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) z2v[q] = fm_ld(rsrc(z.Z2), ru(q), L.ld4, L.vo);
+#pragma unroll
+    for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) z1v[ob][q] = fm_ld(rsrc(z.Z1), 32 * ob + ru(q), L.ld4, L.vo);
+  }
+  auto z2at = [&](int q) {
+    if constexpr (kPre) return z2v[q];
+    else return fm_ld(rsrc(z.Z2), ru(q), L.ld4, L.vo);
+  };
+  auto z1at = [&](int ob, int q) {
+    if constexpr (kPre) return ob ? z1v[1][q] : z1v[0][q];
+    else return fm_ld(rsrc(z.Z1), 32 * ob + ru(q), L.ld4, L.vo);
+  };
+  f32x16 dp3[1];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int u = ru(q) + L.h4;
+    const float t = t3v[q];
+    dp3[0][q] = u < C::AC ? dca[0][q] * limv[q] * (1.f - t * t) : 0.f;
+  }
+  SPP_TPN(23);  // ACM bwd input
+  dense<1, C::RV_AC, C::BF>(p.acm.W3T, 1, dp3, nullptr, [&](int ob, const f32x16& acc) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const float zz = z2at(q);
+      L.sl[ru(q) * 32] = acc[q] * (1.f - zz * zz);
+    }
+  });
+  SPP_TPN(24);  // ACM W3T
+  f32x16 dp2[1];
+  lds_load<1>(dp2, small);
+  dense<1, C::RV_Z2, C::BF>(p.acm.W2T, 2, dp2, nullptr, [&](int ob, const f32x16& acc) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const float zz = z1at(ob, q);
+      L.sl[(32 * ob + ru(q)) * 32] = acc[q] * (1.f - zz * zz);
+    }
+  });
+  SPP_TPN(25);  // ACM W2T
+  f32x16 dp1[2];
+  lds_load<2>(dp1, small);
+  dense<2, C::RV_Z1, C::BF>(p.acm.W1Ta, C::NB_AOUT, dp1, nullptr, [&](int ob, const f32x16& acc) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int ur = 32 * ob + ru(q);
+      if (ur + L.h4 < C::AOUT) L.bl[ur * 32] = acc[q];
+    }
+  });
+}
+// d (critic action input) -> d a_d in the image rows [0, AOUT): through the ACM, or as it is
+template <class C, bool PRE>
+__device__ __forceinline__ void dca_to_dad(const SacArgs& p, const AcmScratch& z, const Lane& L, float* small,
+                                           const f32x16 (&dca)[C::NB_CA]) {
+  if constexpr (C::ACMC) {
+    acm_backward<C, PRE>(p, z, L, small, dca);
+  } else {
+#pragma unroll
+    for (int ib = 0; ib < C::NB_CA; ++ib)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int ur = 32 * ib + ru(q);
+        if (ur + L.h4 < C::AOUT) L.bl[ur * 32] = dca[ib][q];
+      }
+  }
+}
+
+// Heads backward in the pairing layout (squash, denorm, custom loss, logpi) for narrow heads (NB_PAIR <= 2):
+// hd holds the heads (PARK: they are read back from the ADH rows instead) and returns d loss / d heads, which
+// is also stored to ADH; d loss / d a_d is read from the image rows [0, AOUT).  Returns the custom-loss partial.
+template <class C, bool PARK>
+__device__ __forceinline__ float heads_backward(const SacArgs& p, const Lane& L, f32x16 (&hd)[C::NB_PAIR], bool valid,
+                                                float g_lp) {
+  constexpr bool kParkHeads = PARK;
+  float dist_part = 0.f;
+  const float cl_scale = valid ? p.custom_loss * 2.f * p.inv_B / (float)C::AOUT : 0.f;
+  const int h8 = 8 * L.h;
+  {
+    // Branch-free over the pairing slots: every lane loads through resources bounded to the
+    // arrays (slots j >= AOUT read 0) and computes; results of those slots are dropped.  Per-slot
+    // branches would put each load and its use in one block, i.e. one round trip per slot.
+    const rsrc_t adhr = rsrc_n(p.ADH, 2 * C::AOUT * L.ld4);
+    const rsrc_t epsr = rsrc_n(p.EPS2, C::AOUT * L.ld4);
+    const rsrc_t s2r = rsrc_n(p.S2, C::OB * L.ld4);
+    const bool closs = p.custom_loss != 0.f;
+    SPP_XLANE_SYNC();  // d loss / d a_d was written in the natural layout (other lanes' rows)
+#pragma unroll
+    for (int ib = 0; ib < C::NB_PAIR; ++ib)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int j0 = 16 * ib + r;
+        const int j = j0 + h8;
+        const bool ok = j < C::AOUT;
+        const int jj = ok ? j : 0;
+        const float mu = kParkHeads ? fm_ldb(adhr, j0, L.ld4, L.vp) : hd[ib][r];
+        const float lsr = kParkHeads ? fm_ldb(adhr, C::AOUT + j0, L.ld4, L.vp) : hd[ib][r + 8];
+        const float e = fm_ldb(epsr, j0, L.ld4, L.vp);
+        const float s2 = closs ? fm_ldb(s2r, j0, L.ld4, L.vp) : 0.f;
+        const float ls = fminf(fmaxf(lsr, -20.f), 2.f);
+        const float sc = expf(ls);
+        const float u = fadd_rn(mu, fmul_rn(e, sc));
+        const float d = fsub_rn(u, mu);
+        const float t = tanhf(u);
+        const float lim = actor_lim<true>(p, L.tbl, jj);
+        const float a = fmul_rn(t, lim);
+        float g_ad = L.pl[j0 * 32];  // from the critics through the ACM
+        float g_a = 0.f;
+        if (closs) {
+          if (p.norm_closs) {
+            const float df = fsub_rn(a, normalize<true>(p, L.tbl, jj, s2));
+            g_a += cl_scale * df;
+            dist_part += (valid && ok) ? df * df : 0.f;
+          } else {
+            const float df = fsub_rn(denorm<true>(p, L.tbl, jj, a), s2);
+            g_ad += cl_scale * df;
+            dist_part += (valid && ok) ? df * df : 0.f;
+          }
+        }
+        g_a += g_ad * denorm_scale<true>(p, L.tbl, jj);
+        const float var = fmul_rn(sc, sc);
+        const float sig_m2u = 1.f / (1.f + expf(2.f * u));  // sigmoid(-2u)
+        const float gu = g_a * lim * (1.f - t * t) + g_lp * (-d / var + 2.f - 4.f * sig_m2u);
+        const float gmu = gu + g_lp * d / var;
+        const float gsc = gu * e + g_lp * (d * d / (var * sc) - 1.f / sc);
+        const float gls = (lsr >= -20.f && lsr <= 2.f) ? gsc * sc : 0.f;
+        hd[ib][r] = ok ? gmu : 0.f;
+        hd[ib][r + 8] = ok ? gls : 0.f;
+      }
+    // stores after all of the loop's loads (a buffer store would order every later load behind it)
+#pragma unroll
+    for (int ib = 0; ib < C::NB_PAIR; ++ib)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int j0 = 16 * ib + r;
+        if (j0 + h8 < C::AOUT) {
+          fm_st(rsrc(p.ADH), j0, L.ld4, L.vp, hd[ib][r]);
+          fm_st(rsrc(p.ADH), C::AOUT + j0, L.ld4, L.vp, hd[ib][r + 8]);
+        }
+      }
+  }
+  return dist_part;
+}
+
+// SPLIT (the min-critic split, fp32 sets): the kernel ends after q = min(Q1, Q2) and hands the rest of the
+// phase to k_sac_minq_backward (the chosen critic's backward, samples regrouped by critic) and
+// k_sac_actor_heads<C, true> (everything after it, in the original sample order).
+template <class C, bool SPLIT = false>
 __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratch z) {
   __shared__ float smem[kWavesPerWG * kLdsPerWave];
   __shared__ __attribute__((aligned(16))) float tbl[kTabMax];
@@ -734,7 +915,9 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
     SPP_TP(28);  // squash
     // Wide heads (Ant): park mu / raw log-std in the ADH rows the heads backward overwrites
     // (same lane, same element), instead of keeping NB_PAIR tiles live through the critics.
-    constexpr bool kParkHeads = C::NB_PAIR > 2;
+    // The split forward kernel parks them for k_sac_actor_heads whatever their width.
+    constexpr bool kWide = C::NB_PAIR > 2;
+    constexpr bool kParkHeads = kWide || SPLIT;
     if constexpr (kParkHeads) {
 #pragma unroll
       for (int ib = 0; ib < C::NB_PAIR; ++ib)
@@ -768,6 +951,32 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
     const float dqa = q1 < q2 ? gq : (q1 == q2 ? 0.5f * gq : 0.f);
     const float dqb = q2 < q1 ? gq : (q1 == q2 ? 0.5f * gq : 0.f);
     SPP_TP(19);  // q min (the critic layers themselves: slots 30, 31)
+    if constexpr (SPLIT) {
+      // Hand over: who takes the gradient (dqa != 0: bit 0, dqb != 0: bit 1), both critics' masks, the
+      // tile's list counts, the trunk's masks and the loss partials that need logpi / qmin.
+      const int sel = valid ? (int)(q1 <= q2) | ((int)(q2 <= q1) << 1) : 0;
+      if (L.h == 0) z.SEL[b] = (uint8_t)sel;
+      uint4* cm0 = reinterpret_cast<uint4*>(z.CM + ((int64_t)b * 2 + L.h) * 4);
+      uint4* cm1 = reinterpret_cast<uint4*>(z.CM + (((int64_t)ld + b) * 2 + L.h) * 4);
+      cm0[0] = make_uint4((uint32_t)ma0, (uint32_t)(ma0 >> 32), (uint32_t)ma1, (uint32_t)(ma1 >> 32));
+      cm0[1] = make_uint4((uint32_t)ma2, (uint32_t)(ma2 >> 32), (uint32_t)ma3, (uint32_t)(ma3 >> 32));
+      cm1[0] = make_uint4((uint32_t)mb0, (uint32_t)(mb0 >> 32), (uint32_t)mb1, (uint32_t)(mb1 >> 32));
+      cm1[1] = make_uint4((uint32_t)mb2, (uint32_t)(mb2 >> 32), (uint32_t)mb3, (uint32_t)(mb3 >> 32));
+      const int n1 = __popcll(__ballot(L.h == 0 && (sel & 1))), n2 = __popcll(__ballot(L.h == 0 && (sel & 2)));
+      uint64_t* mk = z.MASK + (int64_t)tile * 4 * 64 + lane;
+      mk[0] = a1lo;
+      mk[64] = a1hi;
+      mk[128] = a2lo;
+      mk[192] = a2hi;
+      const float ps = wave_sum((valid && L.h == 0) ? fsub_rn(alpha * lp, qmin) : 0.f);
+      const float pl = wave_sum((valid && L.h == 0) ? lp : 0.f);
+      if (lane == 0) {
+        z.CNT[tile] = (uint32_t)n1 | ((uint32_t)n2 << 16);
+        p.part[tile * kParts + 2] = ps;
+        p.part[tile * kParts + 4] = pl;
+      }
+      continue;
+    }
     // ---- back through both critics to their action input
     f32x16 dca[C::NB_CA];
 #pragma unroll
@@ -808,82 +1017,10 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
     }
     SPP_TP(31);  // critics backward
     // ---- through the frozen ACM to d a_d  (basic_model.py:118-126 backward)
-    if constexpr (C::ACMC) {
-      // Every scratch value of the three layers is requested up front: buffer loads cannot be
-      // moved across the epilogues' LDS stores (no alias proof), so loads issued inside an
-      // epilogue run as one round trip each.
-      // (Wide-head configs keep the per-element loads: their registers are taken.)
-      constexpr bool kPre = !kParkHeads;
-      float t3v[16], limv[16], z2v[16], z1v[2][16];
-      const rsrc_t t3r = rsrc_n(z.T3, C::AC * L.ld4);  // rows >= AC read 0
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int u = ru(q) + L.h4;
-        t3v[q] = fm_ldb(t3r, ru(q), L.ld4, L.vo);
-        limv[q] = acm_lim<true>(p, L.tbl, u < C::AC ? u : 0);
-      }
-      if constexpr (kPre) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) z2v[q] = fm_ld(rsrc(z.Z2), ru(q), L.ld4, L.vo);
-#pragma unroll
-        for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) z1v[ob][q] = fm_ld(rsrc(z.Z1), 32 * ob + ru(q), L.ld4, L.vo);
-      }
-      auto z2at = [&](int q) {
-        if constexpr (kPre) return z2v[q];
-        else return fm_ld(rsrc(z.Z2), ru(q), L.ld4, L.vo);
-      };
-      auto z1at = [&](int ob, int q) {
-        if constexpr (kPre) return ob ? z1v[1][q] : z1v[0][q];
-        else return fm_ld(rsrc(z.Z1), 32 * ob + ru(q), L.ld4, L.vo);
-      };
-      f32x16 dp3[1];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int u = ru(q) + L.h4;
-        const float t = t3v[q];
-        dp3[0][q] = u < C::AC ? dca[0][q] * limv[q] * (1.f - t * t) : 0.f;
-      }
-      SPP_TPN(23);  // ACM bwd input
-      dense<1, C::RV_AC, C::BF>(p.acm.W3T, 1, dp3, nullptr, [&](int ob, const f32x16& acc) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const float zz = z2at(q);
-          L.sl[ru(q) * 32] = acc[q] * (1.f - zz * zz);
-        }
-      });
-      SPP_TPN(24);  // ACM W3T
-      f32x16 dp2[1];
-      lds_load<1>(dp2, small);
-      dense<1, C::RV_Z2, C::BF>(p.acm.W2T, 2, dp2, nullptr, [&](int ob, const f32x16& acc) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const float zz = z1at(ob, q);
-          L.sl[(32 * ob + ru(q)) * 32] = acc[q] * (1.f - zz * zz);
-        }
-      });
-      SPP_TPN(25);  // ACM W2T
-      f32x16 dp1[2];
-      lds_load<2>(dp1, small);
-      dense<2, C::RV_Z1, C::BF>(p.acm.W1Ta, C::NB_AOUT, dp1, nullptr, [&](int ob, const f32x16& acc) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int ur = 32 * ob + ru(q);
-          if (ur + L.h4 < C::AOUT) L.bl[ur * 32] = acc[q];
-        }
-      });
-    } else {
-#pragma unroll
-      for (int ib = 0; ib < C::NB_CA; ++ib)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int ur = 32 * ib + ru(q);
-          if (ur + L.h4 < C::AOUT) L.bl[ur * 32] = dca[ib][q];
-        }
-    }
+    // (Wide-head configs keep the per-element scratch loads: their registers are taken.)
+    dca_to_dad<C, !kWide>(p, z, L, small, dca);
     SPP_TP(16);  // ACM backward
-    if constexpr (kParkHeads) {
+    if constexpr (kWide) {
       // Wide heads: the heads and trunk backward run in k_sac_actor_heads (a second kernel with
       // the whole register file: in one kernel the live ranges spill to scratch, and spilled
       // phase kernels have returned wrong results).  Hand over d a_d and the masks.
@@ -910,72 +1047,7 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
     }
     // ---- heads backward in the pairing layout (squash, denorm, custom loss, logpi)
     float sac_part = (valid && L.h == 0) ? fsub_rn(alpha * lp, qmin) : 0.f;
-    float dist_part = 0.f;
-    const float cl_scale = valid ? p.custom_loss * 2.f * p.inv_B / (float)C::AOUT : 0.f;
-    const int h8 = 8 * L.h;
-    {
-      // Branch-free over the pairing slots: every lane loads through resources bounded to the
-      // arrays (slots j >= AOUT read 0) and computes; results of those slots are dropped.  Per-slot
-      // branches would put each load and its use in one block, i.e. one round trip per slot.
-      const rsrc_t adhr = rsrc_n(p.ADH, 2 * C::AOUT * L.ld4);
-      const rsrc_t epsr = rsrc_n(p.EPS2, C::AOUT * L.ld4);
-      const rsrc_t s2r = rsrc_n(p.S2, C::OB * L.ld4);
-      const bool closs = p.custom_loss != 0.f;
-      SPP_XLANE_SYNC();  // d loss / d a_d was written in the natural layout (other lanes' rows)
-  #pragma unroll
-      for (int ib = 0; ib < C::NB_PAIR; ++ib)
-  #pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          const int j0 = 16 * ib + r;
-          const int j = j0 + h8;
-          const bool ok = j < C::AOUT;
-          const int jj = ok ? j : 0;
-          const float mu = kParkHeads ? fm_ldb(adhr, j0, L.ld4, L.vp) : hd[ib][r];
-          const float lsr = kParkHeads ? fm_ldb(adhr, C::AOUT + j0, L.ld4, L.vp) : hd[ib][r + 8];
-          const float e = fm_ldb(epsr, j0, L.ld4, L.vp);
-          const float s2 = closs ? fm_ldb(s2r, j0, L.ld4, L.vp) : 0.f;
-          const float ls = fminf(fmaxf(lsr, -20.f), 2.f);
-          const float sc = expf(ls);
-          const float u = fadd_rn(mu, fmul_rn(e, sc));
-          const float d = fsub_rn(u, mu);
-          const float t = tanhf(u);
-          const float lim = actor_lim<true>(p, L.tbl, jj);
-          const float a = fmul_rn(t, lim);
-          float g_ad = L.pl[j0 * 32];  // from the critics through the ACM
-          float g_a = 0.f;
-          if (closs) {
-            if (p.norm_closs) {
-              const float df = fsub_rn(a, normalize<true>(p, L.tbl, jj, s2));
-              g_a += cl_scale * df;
-              dist_part += (valid && ok) ? df * df : 0.f;
-            } else {
-              const float df = fsub_rn(denorm<true>(p, L.tbl, jj, a), s2);
-              g_ad += cl_scale * df;
-              dist_part += (valid && ok) ? df * df : 0.f;
-            }
-          }
-          g_a += g_ad * denorm_scale<true>(p, L.tbl, jj);
-          const float var = fmul_rn(sc, sc);
-          const float sig_m2u = 1.f / (1.f + expf(2.f * u));  // sigmoid(-2u)
-          const float gu = g_a * lim * (1.f - t * t) + g_lp * (-d / var + 2.f - 4.f * sig_m2u);
-          const float gmu = gu + g_lp * d / var;
-          const float gsc = gu * e + g_lp * (d * d / (var * sc) - 1.f / sc);
-          const float gls = (lsr >= -20.f && lsr <= 2.f) ? gsc * sc : 0.f;
-          hd[ib][r] = ok ? gmu : 0.f;
-          hd[ib][r + 8] = ok ? gls : 0.f;
-        }
-      // stores after all of the loop's loads (a buffer store would order every later load behind it)
-  #pragma unroll
-      for (int ib = 0; ib < C::NB_PAIR; ++ib)
-  #pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          const int j0 = 16 * ib + r;
-          if (j0 + h8 < C::AOUT) {
-            fm_st(rsrc(p.ADH), j0, L.ld4, L.vp, hd[ib][r]);
-            fm_st(rsrc(p.ADH), C::AOUT + j0, L.ld4, L.vp, hd[ib][r + 8]);
-          }
-        }
-    }
+    const float dist_part = heads_backward<C, false>(p, L, hd, valid, g_lp);
     SPP_TP(17);  // heads backward
     // ---- dh2 = Wh^T dheads * relu'(h2); dh1 = W2^T dh2 * relu'(h1)
     dense<C::NB_PAIR, C::RV_PAIR, C::BF>(p.actor.WhT, 8, hd, nullptr, [&](int ob, const f32x16& acc) {
@@ -1007,6 +1079,93 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
   SPP_TP_FLUSH();
 }
 
+// Heads backward for wide heads (NB_PAIR > 2; k_sac_actor_heads): the heads are parked in the ADH rows, d loss / d a_d
+// comes from z.GAD, or (IMG) from the image rows [0, AOUT), which the loop overwrites only behind its reads: block
+// ib's results go to the rows it has just read and to rows >= AOUT.  hd returns d loss / d heads, also stored to ADH.
+template <class C, bool IMG>
+__device__ __forceinline__ float heads_backward_wide(const SacArgs& p, const AcmScratch& z, const Lane& L,
+                                                     f32x16 (&hd)[C::NB_PAIR], bool valid, float g_lp) {
+  float dist_part = 0.f;
+  const float cl_scale = valid ? p.custom_loss * 2.f * p.inv_B / (float)C::AOUT : 0.f;
+  const rsrc_t adhr = rsrc_n(p.ADH, 2 * C::AOUT * L.ld4);
+  const rsrc_t epsr = rsrc_n(p.EPS2, C::AOUT * L.ld4);
+  const rsrc_t s2r = rsrc_n(p.S2, C::OB * L.ld4);
+  const rsrc_t gr = rsrc_n(z.GAD, C::AOUT * L.ld4);
+  const bool closs = p.custom_loss != 0.f;
+  const int h8 = 8 * L.h;
+  if constexpr (IMG) SPP_XLANE_SYNC();  // d loss / d a_d was written in the natural layout (other lanes' rows)
+  // one pairing block per iteration (not unrolled: a block's loads and math stay within the
+  // iteration); results go to the LDS image in the pairing layout (rows j / AOUT + j)
+#pragma unroll 1
+  for (int ib = 0; ib < C::NB_PAIR; ++ib) {
+    float mu[8], lsr[8], ev[8], s2v[8], gv[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int j0 = 16 * ib + r;
+      mu[r] = fm_ldb(adhr, j0, L.ld4, L.vp);
+      lsr[r] = fm_ldb(adhr, C::AOUT + j0, L.ld4, L.vp);
+      ev[r] = fm_ldb(epsr, j0, L.ld4, L.vp);
+      s2v[r] = closs ? fm_ldb(s2r, j0, L.ld4, L.vp) : 0.f;
+      if constexpr (IMG) gv[r] = j0 + h8 < C::AOUT ? L.pl[j0 * 32] : 0.f;
+      else gv[r] = fm_ldb(gr, j0, L.ld4, L.vp);
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int j0 = 16 * ib + r;
+      const int j = j0 + h8;
+      const bool ok = j < C::AOUT;
+      const int jj = ok ? j : 0;
+      constexpr bool F = C::BF;
+      const float e = ev[r];
+      const float ls = fminf(fmaxf(lsr[r], -20.f), 2.f);
+      const float sc = t_exp<F>(ls);
+      const float u = fadd_rn(mu[r], fmul_rn(e, sc));
+      const float d = fsub_rn(u, mu[r]);
+      const float t = t_tanh<F>(u);
+      const float lim = actor_lim<true>(p, L.tbl, jj);
+      const float a = fmul_rn(t, lim);
+      float g_ad = gv[r];  // from the critics through the ACM
+      float g_a = 0.f;
+      if (closs) {
+        if (p.norm_closs) {
+          const float df = fsub_rn(a, normalize<true>(p, L.tbl, jj, s2v[r]));
+          g_a += cl_scale * df;
+          dist_part += (valid && ok) ? df * df : 0.f;
+        } else {
+          const float df = fsub_rn(denorm<true>(p, L.tbl, jj, a), s2v[r]);
+          g_ad += cl_scale * df;
+          dist_part += (valid && ok) ? df * df : 0.f;
+        }
+      }
+      g_a += g_ad * denorm_scale<true>(p, L.tbl, jj);
+      const float var = fmul_rn(sc, sc);
+      const float ivar = t_rcp<F>(var), isc = t_rcp<F>(sc);
+      const float sig_m2u = t_rcp<F>(1.f + t_exp<F>(2.f * u));  // sigmoid(-2u)
+      const float gu = g_a * lim * (1.f - t * t) + g_lp * (-d * ivar + 2.f - 4.f * sig_m2u);
+      const float gmu = gu + g_lp * d * ivar;
+      const float gsc = gu * e + g_lp * (d * d * ivar * isc - isc);
+      const float gls = (lsr[r] >= -20.f && lsr[r] <= 2.f) ? gsc * sc : 0.f;
+      if (ok) {  // slot j >= AOUT would land on row AOUT + j' of a valid slot's log-std
+        L.pl[j0 * 32] = gmu;
+        L.pl[(C::AOUT + j0) * 32] = gls;
+      }
+    }
+  }
+  load_pair<C>(hd, L.img);
+  // the heads' gradient operands (dW of fc_prob / fc_scale), after every load above
+#pragma unroll
+  for (int ib = 0; ib < C::NB_PAIR; ++ib)
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int j0 = 16 * ib + r;
+      if (j0 + h8 < C::AOUT) {
+        fm_st(rsrc(p.ADH), j0, L.ld4, L.vp, hd[ib][r]);
+        fm_st(rsrc(p.ADH), C::AOUT + j0, L.ld4, L.vp, hd[ib][r + 8]);
+      }
+    }
+  return dist_part;
+}
+
 // ============================================================================ actor phase, wide heads
 // k_sac_actor_heads: the heads backward (squash, denormalisation, custom loss, logpi, in the
 // pairing layout) and the trunk backward of the actor phase for wide heads (Ant), after
@@ -1014,7 +1173,12 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
 // pairing block at a time: the block's parked heads, eps, targets and d a_d are requested together
 // (one round trip per block), the limit / normaliser vectors come from the LDS table, and the
 // results stay in registers (the WhT layer's input tile) until every load has been issued.
-template <class C>
+//
+// SPLIT (the min-critic split, any head width): the kernel is everything behind the critics' backward.  It
+// sums the chosen critics' action-input gradients (z.DCA, selected by z.SEL), runs the frozen-ACM backward
+// into the image, and then the heads backward of the set's width (d a_d is read from the image, not from
+// z.GAD) and the trunk backward.
+template <class C, bool SPLIT = false>
 __global__ __launch_bounds__(256, 1) void k_sac_actor_heads(SacArgs p, AcmScratch z) {
   __shared__ float smem[kWavesPerWG * kLdsPerWave];
   __shared__ __attribute__((aligned(16))) float tbl[kTabMax];
@@ -1030,85 +1194,40 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_heads(SacArgs p, AcmScratc
     const Lane L = make_lane(big, small, tbl, ld, tile * 32 + (lane & 31));
     const bool valid = L.b < p.B;
     const float g_lp = valid ? alpha * p.inv_B : 0.f;
+    constexpr bool kWide = C::NB_PAIR > 2;
+    if constexpr (SPLIT) {
+      // dca = 0; dca += critic 1's; dca += critic 2's, as the one-kernel phase sums them: there the critic
+      // that lost the min adds the exact +0 its zero delta2 gives.  Rows >= CA are not read by anything.
+      const int sel = z.SEL[L.b];
+      const rsrc_t r1 = rsrc_n(z.DCA[0], C::CA * L.ld4), r2 = rsrc_n(z.DCA[1], C::CA * L.ld4);
+      f32x16 dca[C::NB_CA];
+#pragma unroll
+      for (int ib = 0; ib < C::NB_CA; ++ib)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int ur = 32 * ib + ru(q);
+          float v1 = 0.f, v2 = 0.f;
+          if (ur < C::CA) {  // (rows ur + 4h >= CA of the upper lane half read 0 through the bounded resource)
+            v1 = fm_ldb(r1, ur, L.ld4, L.vo);
+            v2 = fm_ldb(r2, ur, L.ld4, L.vo);
+          }
+          v1 = (sel & 1) ? v1 : 0.f;
+          v2 = (sel & 2) ? v2 : 0.f;
+          dca[ib][q] = fadd_rn(fadd_rn(0.f, v1), v2);
+        }
+      SPP_TP(31);  // critics backward (here: its results read back)
+      dca_to_dad<C, true>(p, z, L, small, dca);
+      SPP_TP(16);  // ACM backward
+    }
     const uint64_t* mk = z.MASK + (int64_t)tile * 4 * 64 + lane;
     const uint64_t a1lo = mk[0], a1hi = mk[64], a2lo = mk[128], a2hi = mk[192];
     float dist_part = 0.f;
-    const float cl_scale = valid ? p.custom_loss * 2.f * p.inv_B / (float)C::AOUT : 0.f;
-    const rsrc_t adhr = rsrc_n(p.ADH, 2 * C::AOUT * L.ld4);
-    const rsrc_t epsr = rsrc_n(p.EPS2, C::AOUT * L.ld4);
-    const rsrc_t s2r = rsrc_n(p.S2, C::OB * L.ld4);
-    const rsrc_t gr = rsrc_n(z.GAD, C::AOUT * L.ld4);
-    const bool closs = p.custom_loss != 0.f;
-    const int h8 = 8 * L.h;
-    // one pairing block per iteration (not unrolled: a block's loads and math stay within the
-    // iteration); results go to the LDS image in the pairing layout (rows j / AOUT + j)
-#pragma unroll 1
-    for (int ib = 0; ib < C::NB_PAIR; ++ib) {
-      float mu[8], lsr[8], ev[8], s2v[8], gv[8];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int j0 = 16 * ib + r;
-        mu[r] = fm_ldb(adhr, j0, L.ld4, L.vp);
-        lsr[r] = fm_ldb(adhr, C::AOUT + j0, L.ld4, L.vp);
-        ev[r] = fm_ldb(epsr, j0, L.ld4, L.vp);
-        s2v[r] = closs ? fm_ldb(s2r, j0, L.ld4, L.vp) : 0.f;
-        gv[r] = fm_ldb(gr, j0, L.ld4, L.vp);
-      }
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int j0 = 16 * ib + r;
-        const int j = j0 + h8;
-        const bool ok = j < C::AOUT;
-        const int jj = ok ? j : 0;
-        constexpr bool F = C::BF;
-        const float e = ev[r];
-        const float ls = fminf(fmaxf(lsr[r], -20.f), 2.f);
-        const float sc = t_exp<F>(ls);
-        const float u = fadd_rn(mu[r], fmul_rn(e, sc));
-        const float d = fsub_rn(u, mu[r]);
-        const float t = t_tanh<F>(u);
-        const float lim = actor_lim<true>(p, L.tbl, jj);
-        const float a = fmul_rn(t, lim);
-        float g_ad = gv[r];  // from the critics through the ACM
-        float g_a = 0.f;
-        if (closs) {
-          if (p.norm_closs) {
-            const float df = fsub_rn(a, normalize<true>(p, L.tbl, jj, s2v[r]));
-            g_a += cl_scale * df;
-            dist_part += (valid && ok) ? df * df : 0.f;
-          } else {
-            const float df = fsub_rn(denorm<true>(p, L.tbl, jj, a), s2v[r]);
-            g_ad += cl_scale * df;
-            dist_part += (valid && ok) ? df * df : 0.f;
-          }
-        }
-        g_a += g_ad * denorm_scale<true>(p, L.tbl, jj);
-        const float var = fmul_rn(sc, sc);
-        const float ivar = t_rcp<F>(var), isc = t_rcp<F>(sc);
-        const float sig_m2u = t_rcp<F>(1.f + t_exp<F>(2.f * u));  // sigmoid(-2u)
-        const float gu = g_a * lim * (1.f - t * t) + g_lp * (-d * ivar + 2.f - 4.f * sig_m2u);
-        const float gmu = gu + g_lp * d * ivar;
-        const float gsc = gu * e + g_lp * (d * d * ivar * isc - isc);
-        const float gls = (lsr[r] >= -20.f && lsr[r] <= 2.f) ? gsc * sc : 0.f;
-        if (ok) {  // slot j >= AOUT would land on row AOUT + j' of a valid slot's log-std
-          L.pl[j0 * 32] = gmu;
-          L.pl[(C::AOUT + j0) * 32] = gls;
-        }
-      }
-    }
     f32x16 hd[C::NB_PAIR];
-    load_pair<C>(hd, big);
-    // the heads' gradient operands (dW of fc_prob / fc_scale), after every load above
-#pragma unroll
-    for (int ib = 0; ib < C::NB_PAIR; ++ib)
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int j0 = 16 * ib + r;
-        if (j0 + h8 < C::AOUT) {
-          fm_st(rsrc(p.ADH), j0, L.ld4, L.vp, hd[ib][r]);
-          fm_st(rsrc(p.ADH), C::AOUT + j0, L.ld4, L.vp, hd[ib][r + 8]);
-        }
-      }
+    if constexpr (!kWide) {
+      dist_part = heads_backward<C, true>(p, L, hd, valid, g_lp);
+    } else {
+      dist_part = heads_backward_wide<C, SPLIT>(p, z, L, hd, valid, g_lp);
+    }
     SPP_TP(17);  // heads backward
     // ---- dh2 = Wh^T dheads * relu'(h2); dh1 = W2^T dh2 * relu'(h1)
     dense<C::NB_PAIR, C::RV_PAIR, C::BF>(p.actor.WhT, 8, hd, nullptr, [&](int ob, const f32x16& acc) {
@@ -1131,6 +1250,134 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_heads(SacArgs p, AcmScratc
   }
   SPP_TP_FLUSH();
 }
+
+// ============================================================================ actor phase, min-critic split
+// k_sac_minq_backward: the critics' backward to their action input, for the critic(s) whose Q took the min only.
+// The actor loss uses min(Q1, Q2), so per sample the other critic's upstream gradient is exactly 0 (an exact tie
+// gives each 1/2), and its W2^T / W1^T a MFMAs multiply zeros.  Samples are the MFMA's N dimension and the two
+// critics have different weights, so the zeros can only be skipped by regrouping the samples by critic over the
+// whole batch: a group is 32 entries of one critic's list (k_minq_scatter), and the two lists give
+// ceil(n1 / 32) + ceil(n2 / 32) groups where the one-kernel phase runs 2 * Bp / 32 critic tiles.  An MFMA output
+// column depends on its own input column only, so a sample's values do not depend on the group or lane it lands
+// in.  The results go to the sample's own column of z.DCA[critic]; k_sac_actor_heads<C, true> adds them.
+template <class C>
+__global__ __launch_bounds__(256, 1) void k_sac_minq_backward(SacArgs p, AcmScratch z) {
+  __shared__ float smem[kWavesPerWG * kLdsPerWave];
+  __shared__ __attribute__((aligned(16))) float tbl[kTabMax];
+  SPP_TP_INIT();
+  load_table(p, tbl);
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  float* big = smem + w * kLdsPerWave;
+  float* small = big + kSmallRow * 32;
+  const int ld = p.Bp;
+  const int n1 = z.NG[0], n2 = z.NG[1];  // <= B each
+  const int g1 = (n1 + 31) >> 5, ngroups = g1 + ((n2 + 31) >> 5);
+  for (int g = blockIdx.x * kWavesPerWG + w; g < ngroups; g += gridDim.x * kWavesPerWG) {
+    const int i = g >= g1;  // this group's critic (wave-uniform)
+    const int pos = 32 * (i ? g - g1 : g) + (lane & 31);
+    const bool live = pos < (i ? n2 : n1);  // padding lanes of a list's last group: dq = 0, nothing stored
+    const int b = live ? z.LIST[i][pos] : 0;
+    const Lane L = make_lane(big, small, tbl, ld, b);
+    const uint4* cm = reinterpret_cast<const uint4*>(z.CM + (((int64_t)i * ld + b) * 2 + L.h) * 4);
+    const uint4 c01 = cm[0], c23 = cm[1];
+    const int sel = z.SEL[b];
+    const uint64_t k0 = live ? (uint64_t)c01.x | ((uint64_t)c01.y << 32) : 0;
+    const uint64_t k1 = live ? (uint64_t)c01.z | ((uint64_t)c01.w << 32) : 0;
+    const uint64_t k2 = live ? (uint64_t)c23.x | ((uint64_t)c23.y << 32) : 0;
+    const uint64_t k3 = live ? (uint64_t)c23.z | ((uint64_t)c23.w << 32) : 0;
+    // torch.minimum backward: ties split the gradient in half (list entries are samples b < B)
+    const float gq = -p.inv_B;
+    const float dqi = live ? (sel == 3 ? 0.5f * gq : gq) : 0.f;
+    const CriticDev& Q = p.critic[i];
+    const float* w3 = tbl + Q.tw3;
+    auto epi1 = [&](int ob, const f32x16& acc) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) L.bl[(32 * ob + ru(q)) * 32] = getbit(k0, k1, ob, q) ? acc[q] : 0.f;
+    };
+    if constexpr (C::GEN_AD2) {
+      auto st2 = [](int, float) {};
+      Delta2Gen<8, decltype(st2)> gen{w3, L.h4, k2, k3, dqi, st2, {}};
+      SPP_TPN(20);  // (delta2 is produced under the W2T MFMAs)
+      dense_gen<8>(Q.W2T, nullptr, gen, epi1);
+    } else {
+#pragma unroll 1
+      for (int ob = 0; ob < 8; ++ob) {
+        float tv[16];
+        tvals(w3, ob, L.h4, tv);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) L.bl[(32 * ob + ru(q)) * 32] = getbit(k2, k3, ob, q) ? dqi * tv[q] : 0.f;
+      }
+      SPP_TPN(20);  // delta staging
+      dense_lds<8, C::BF>(Q.W2T, big, nullptr, epi1);
+    }
+    SPP_TPN(21);  // W2T
+    const rsrc_t dr = rsrc(z.DCA[i]);
+    dense_lds<C::NB_CA, C::BF>(Q.W1Ta, big, nullptr, [&](int ob, const f32x16& acc) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int ur = 32 * ob + ru(q);
+        if (ur < C::CA) {
+          if (live && ur + L.h4 < C::CA) fm_st(dr, ur, L.ld4, L.vo, acc[q]);
+        }
+      }
+    });
+    SPP_TPN(22);  // W1Ta
+  }
+  SPP_TP_FLUSH();
+}
+
+#ifndef SPP_KSET_TU  // non-template kernels live in the api.hip translation unit only
+// The two lists of the min-critic split from the per-tile counts (AcmScratch): list i holds the samples whose
+// selector has bit i, ascending (a stable partition by exclusive prefix sums; no atomics).
+// k_minq_scan: one workgroup; thread t sums the counts of its run of consecutive tiles, the runs' sums are
+// scanned in LDS, and the thread walks its run again to write each tile's two list positions.
+constexpr int kMinqScanThreads = 1024;
+__global__ __launch_bounds__(kMinqScanThreads) void k_minq_scan(const uint32_t* CNT, uint32_t* OFF, int* NG, int ntiles) {
+  __shared__ uint32_t s1[kMinqScanThreads], s2[kMinqScanThreads];
+  const int t = threadIdx.x;
+  const int per = (ntiles + kMinqScanThreads - 1) / kMinqScanThreads;
+  const int t0 = min(t * per, ntiles), t1 = min(t0 + per, ntiles);
+  uint32_t a1 = 0, a2 = 0;
+  for (int k = t0; k < t1; ++k) {
+    const uint32_t c = CNT[k];
+    a1 += c & 0xffffu;
+    a2 += c >> 16;
+  }
+  s1[t] = a1;
+  s2[t] = a2;
+  __syncthreads();
+  for (int o = 1; o < kMinqScanThreads; o <<= 1) {  // inclusive scan of the runs' sums
+    const uint32_t u1 = t >= o ? s1[t - o] : 0u, u2 = t >= o ? s2[t - o] : 0u;
+    __syncthreads();
+    s1[t] += u1;
+    s2[t] += u2;
+    __syncthreads();
+  }
+  uint32_t o1 = s1[t] - a1, o2 = s2[t] - a2;
+  for (int k = t0; k < t1; ++k) {
+    const uint32_t c = CNT[k];
+    OFF[2 * k] = o1;
+    OFF[2 * k + 1] = o2;
+    o1 += c & 0xffffu;
+    o2 += c >> 16;
+  }
+  if (t == kMinqScanThreads - 1) {
+    NG[0] = (int)s1[t];
+    NG[1] = (int)s2[t];
+  }
+}
+// k_minq_scatter: one thread per sample (a wave covers two tiles); a sample's rank within its tile comes from
+// the wave ballot, so each list is ascending in the sample index.
+__global__ __launch_bounds__(256) void k_minq_scatter(const uint8_t* SEL, const uint32_t* OFF, int* L1, int* L2, int Bp) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  const int sel = b < Bp ? SEL[b] : 0;
+  const int sh = threadIdx.x & 32;  // this tile's half of the ballot
+  const uint32_t below = (1u << (threadIdx.x & 31)) - 1u;
+  const uint32_t m1 = (uint32_t)(__ballot(sel & 1) >> sh), m2 = (uint32_t)(__ballot(sel & 2) >> sh);
+  if (sel & 1) L1[OFF[2 * (b >> 5)] + __popc(m1 & below)] = b;
+  if (sel & 2) L2[OFF[2 * (b >> 5) + 1] + __popc(m2 & below)] = b;
+}
+#endif  // SPP_KSET_TU
 
 // ============================================================================ rollout action
 struct ActArgs {
