@@ -11,6 +11,7 @@
 
 #include "../../include/spprl.h"
 #include "internal.h"
+#include "layout.h"
 #include "replay.h"
 #include "sac_kernels.h"
 
@@ -790,6 +791,58 @@ struct DwSet {
   void release() { slab.release(); jobs.release(); items.release(); }
 };
 
+// The packed weight images and LDS table segments of one handle (build_packs, onp_packs): M / T record them in
+// call order, commit() places the images in one arena in that order and uploads the job table ordered by list.
+struct PackPlan {
+  struct Image {
+    int list;
+    PackJob job;
+    const float4** slot;  // receives the image's address
+  };
+  std::vector<Image> images;
+  std::vector<TabSeg> tab;
+  int toff = 0;  // floats of the LDS table so far
+  int bf16 = 0;  // bf16 images (PackJob::bf16)
+  // ib = 1: ib-major image for dense_lds (256-input layers)
+  void M(int list, const float* W, const float* W2, int split, int ld, int trans, int coff, MapDesc out, MapDesc in,
+         int NBO, int NBI, const float4** slot, int ib = 0) {
+    images.push_back({list, PackJob{W, W2, split, ld, trans, coff, out, in, NBO, NBI, ib, nullptr, bf16}, slot});
+  }
+  // LDS table: each vector (or pair v | v2) starts on a 32-float boundary, zero padded to a whole block
+  int T(const float* v, int n, const float* v2 = nullptr, int n2 = 0) {
+    const int off = toff, tot = (int)round_up(n + n2, 32);
+    tab.push_back(TabSeg{v, n, v2 ? n : tot, off, 0});
+    if (v2) tab.push_back(TabSeg{v2, n2, tot - n, off + n, 0});
+    toff += tot;
+    return off;
+  }
+  // jobs = the lists back to back (call order inside a list), as uploaded to d_pj; list l = [off[l], off[l + 1])
+  sppStatus commit(int nlists, DevArray<float4>& pk, DevArray<PackJob>& d_pj, std::vector<PackJob>& jobs, int* off) {
+    size_t nf4 = 0;
+    for (auto& m : images) nf4 += (size_t)m.job.NBO * m.job.NBI * 4 * 64;
+    pk.release();
+    SPP_CHECK_HIP(pk.alloc(nf4));
+    size_t of = 0;
+    for (auto& m : images) {
+      m.job.dst = pk.ptr + of;
+      *m.slot = m.job.dst;
+      of += (size_t)m.job.NBO * m.job.NBI * 4 * 64;
+    }
+    jobs.clear();
+    for (int l = 0; l < nlists; ++l) {
+      off[l] = (int)jobs.size();
+      for (auto& m : images)
+        if (m.list == l) jobs.push_back(m.job);
+    }
+    off[nlists] = (int)jobs.size();
+    d_pj.release();
+    SPP_CHECK_HIP(d_pj.alloc(jobs.size()));
+    SPP_CHECK_HIP(hipMemcpy(d_pj.ptr, jobs.data(), sizeof(PackJob) * jobs.size(), hipMemcpyHostToDevice));
+    return SPP_OK;
+  }
+};
+enum { PJ_ACTOR, PJ_ACM, PJ_TARG, PJ_CRITIC, PJ_LISTS };  // the agent handles' pack-job lists, in d_pj order
+
 // dims -> kernel instantiation: one translation unit per config family (ks_*.hip),
 // compiled in parallel by build.py and linked into libspprl.so.
 static bool find_kset(int algo, int ob, int aout, int ac, bool acmc, bool bf16, KernelSet* ks) {
@@ -839,7 +892,7 @@ struct sppAgent {
   bool team_ok = true;  // SPP_SAC_TEAM=0: the one-wave phase kernels at every batch (A/B)
   KernelSet ks{};
   NetBufs net[SPP_NET_COUNT];
-  int64_t nsize[SPP_NET_COUNT] = {};
+  NetLayout lay[SPP_NET_COUNT];  // flat format of each net's parameter / gradient buffer (layout.h); empty: no such net
   int cin = 0, Bmax = 0, Bpmax = 0;
   int64_t steps[4] = {0, 0, 0, 0};  // actor, critic, alpha, acm
   const float *lo = nullptr, *hi = nullptr, *mean = nullptr, *std = nullptr;
@@ -848,14 +901,13 @@ struct sppAgent {
   DevArray<float> limits;  // [aout] actor lim | [ac] acm lim
   // packed images
   DevArray<float4> pk;     // all matrix images
-  std::vector<PackJob> pj_actor, pj_acm, pj_targ, pj_critic_fwd, pj_critic_all, pj_acmreg;
+  std::vector<PackJob> pj;  // the pack jobs as in d_pj: lists [actor | acm | targ | critic]
+  int o_pj[PJ_LISTS + 1] = {};  // list l = jobs [o_pj[l], o_pj[l + 1])
   bool ddpg = false;
   // vanilla SAC (SPP_ALGO_SAC): the ACM net exists but is never evaluated; vanilla DDPG (SPP_ALGO_DDPG,
   // ddpg && plain): there is no ACM net at all
   bool plain = false;
   DevArray<PackJob> d_pj;
-  // job-table offsets inside d_pj
-  int o_actor = 0, o_acm = 0, o_targ = 0, o_cfwd = 0, o_call = 0, o_acmreg = 0;
   // LDS constant-table segments (canonical bias / fc3 vectors, read at kernel start)
   std::vector<TabSeg> tab;
   int tab_floats = 0;  // weight part of the table (make_args appends the limit / normaliser segments)
@@ -914,15 +966,6 @@ static void tmark(sppAgent* a, int kind, hipStream_t st) {
 
 namespace spp {
 
-static int64_t sac_actor_size(int ob, int aout) { return 256LL * ob + 256 + 65536 + 256 + 2LL * (aout * 256 + aout); }
-static int64_t critic_size(int cin) { return 256LL * cin + 256 + 65536 + 256 + 256 + 1; }
-static int64_t acm_size(int in, int ac) { return 64LL * in + 64 + 32 * 64 + 32 + (int64_t)ac * 32 + ac; }
-static int64_t ddpg_actor_size(int ob, int aout) { return 256LL * ob + 256 + 65536 + 256 + (int64_t)aout * 256 + aout; }
-// BasicAcM state_dict: t, t1, fc1, fc2, fc21, fc3 (basic_acm.py:11-21)
-static int64_t bacm_size(int in, int ac) {
-  return 1 + ac + 100LL * in + 100 + 50 * 100 + 50 + 50LL * in + 50 + (int64_t)ac * 50 + ac;
-}
-
 static MapDesc nat(int n) { return MapDesc{MAP_NAT, n, 0, 0, 0}; }
 static MapDesc cat(int n0, int n1) { return MapDesc{MAP_CAT, n0, blocks_of(n0), n1, n0}; }
 static MapDesc pair(int n) { return MapDesc{MAP_PAIR, n, 0, 0, 0}; }
@@ -934,166 +977,117 @@ static sppStatus build_packs(sppAgent* a) {
   const int ob = a->cfg.ob, aout = a->cfg.aout, ac = a->cfg.ac;
   const int ca = a->cfg.acm_critic ? ac : aout;
   const int cin = ob + ca;
-  for (int k = 0; k < SPP_NET_COUNT; ++k) {
-    const bool used = a->ddpg ? (k == SPP_NET_ACTOR || k == SPP_NET_CRITIC1 || k == SPP_NET_CRITIC1_TARG ||
-                                 (k == SPP_NET_ACM && !a->plain) || k == SPP_NET_ACTOR_TARG)
-                              : k != SPP_NET_ACTOR_TARG;
-    SPP_REQUIRE(!used || a->net[k].p, SPP_E_STATE, "network %d parameters not bound", k);
-  }
-  // sizes: count float4 and vector slots first
-  struct MatSpec {
-    std::vector<PackJob>* list;
-    PackJob job;
-    const float4** slot;
-  };
-  std::vector<MatSpec> ms;
-  // ib = 1: ib-major image for dense_lds (256-input layers)
-  auto M = [&](std::vector<PackJob>* list, const float* W, const float* W2, int split, int ld, int trans, int coff,
-               MapDesc out, MapDesc in, int NBO, int NBI, const float4** slot, int ib = 0) {
-    PackJob j{W, W2, split, ld, trans, coff, out, in, NBO, NBI, ib, nullptr, a->cfg.mlp_bf16 ? 1 : 0};
-    ms.push_back({list, j, slot});
-  };
-  // LDS table: each vector starts on a 32-float boundary, zero padded to a whole block
-  a->tab.clear();
-  int toff = 0;
-  auto T = [&](const float* v, int n, const float* v2 = nullptr, int n2 = 0) {
-    const int off = toff, tot = (int)round_up(n + n2, 32);
-    a->tab.push_back(TabSeg{v, n, v2 ? n : tot, off, 0});
-    if (v2) a->tab.push_back(TabSeg{v2, n2, tot - n, off + n, 0});
-    toff += tot;
-    return off;
-  };
+  for (int k = 0; k < SPP_NET_COUNT; ++k)  // every net the handle has (sppAgentCreate)
+    SPP_REQUIRE(a->lay[k].size() == 0 || a->net[k].p, SPP_E_STATE, "network %d parameters not bound", k);
+  PackPlan pp;
+  pp.bf16 = a->cfg.mlp_bf16 ? 1 : 0;
   if (!a->ddpg) {
-    // ---- actor (sac/models.py:12-22): fc1 [256][ob], fc2, fc_prob [aout][256], fc_scale
-    {
-      const float* P = a->net[SPP_NET_ACTOR].p;
-      const float *W1 = P, *b1 = W1 + 256 * ob, *W2 = b1 + 256, *b2 = W2 + 65536, *Wp = b2 + 256, *bp = Wp + aout * 256,
-                  *Ws = bp + aout, *bs = Ws + aout * 256;
-      M(&a->pj_actor, W1, nullptr, 1 << 30, ob, 0, 0, nat(256), nat(ob), 8, blocks_of(ob), &a->actor.W1);
-      M(&a->pj_actor, W2, nullptr, 1 << 30, 256, 0, 0, nat(256), nat(256), 8, 8, &a->actor.W2, 1);
-      M(&a->pj_actor, Wp, Ws, aout, 256, 0, 0, nat(2 * aout), nat(256), blocks_of(2 * aout), 8, &a->actor.Wh, 1);
-      M(&a->pj_actor, W2, nullptr, 1 << 30, 256, 1, 0, nat(256), nat(256), 8, 8, &a->actor.W2T, 1);
-      M(&a->pj_actor, Wp, Ws, aout, 256, 1, 0, nat(256), pair(aout), 8, (aout + 15) / 16, &a->actor.WhT);
-      if (a->cfg.mlp_bf16)  // the two-tile bf16 critic phase squashes in the heads' epilogue (sac_bf.h)
-        M(&a->pj_actor, Wp, Ws, aout, 256, 0, 0, pair(aout), nat(256), (aout + 15) / 16, 8, &a->actor.WhP, 1);
-      a->actor.tb1 = T(b1, 256);
-      a->actor.tb2 = T(b2, 256);
-      a->actor.tbh = T(bp, aout, bs, aout);
-    }
+    // ---- actor: fc1 [256][ob], fc2, fc_prob [aout][256], fc_scale
+    const float* P = a->net[SPP_NET_ACTOR].p;
+    const NetLayout& L = a->lay[SPP_NET_ACTOR];
+    const float *W1 = P + L.w(0), *W2 = P + L.w(1), *Wp = P + L.w(kFcProb), *Ws = P + L.w(kFcScale);
+    pp.M(PJ_ACTOR, W1, nullptr, 1 << 30, ob, 0, 0, nat(256), nat(ob), 8, blocks_of(ob), &a->actor.W1);
+    pp.M(PJ_ACTOR, W2, nullptr, 1 << 30, 256, 0, 0, nat(256), nat(256), 8, 8, &a->actor.W2, 1);
+    pp.M(PJ_ACTOR, Wp, Ws, aout, 256, 0, 0, nat(2 * aout), nat(256), blocks_of(2 * aout), 8, &a->actor.Wh, 1);
+    pp.M(PJ_ACTOR, W2, nullptr, 1 << 30, 256, 1, 0, nat(256), nat(256), 8, 8, &a->actor.W2T, 1);
+    pp.M(PJ_ACTOR, Wp, Ws, aout, 256, 1, 0, nat(256), pair(aout), 8, (aout + 15) / 16, &a->actor.WhT);
+    if (a->cfg.mlp_bf16)  // the two-tile bf16 critic phase squashes in the heads' epilogue (sac_bf.h)
+      pp.M(PJ_ACTOR, Wp, Ws, aout, 256, 0, 0, pair(aout), nat(256), (aout + 15) / 16, 8, &a->actor.WhP, 1);
+    a->actor.tb1 = pp.T(P + L.b(0), 256);
+    a->actor.tb2 = pp.T(P + L.b(1), 256);
+    a->actor.tbh = pp.T(P + L.b(kFcProb), aout, P + L.b(kFcScale), aout);
   } else {
-    // ---- DDPG actor and its target (ddpg/models.py:5-22): fc1 [256][ob], fc2, fc3 [aout][256]
+    // ---- DDPG actor and its target: fc1 [256][ob], fc2, fc3 [aout][256]
     for (int t = 0; t < 2; ++t) {
-      const float* P = a->net[t == 0 ? SPP_NET_ACTOR : SPP_NET_ACTOR_TARG].p;
+      const int netid = t == 0 ? SPP_NET_ACTOR : SPP_NET_ACTOR_TARG;
+      const float* P = a->net[netid].p;
+      const NetLayout& L = a->lay[netid];
       ActorDev& ad = t == 0 ? a->actor : a->actor_targ;
-      std::vector<PackJob>* l = t == 0 ? &a->pj_actor : &a->pj_targ;
-      const float *W1 = P, *b1 = W1 + 256 * ob, *W2 = b1 + 256, *b2 = W2 + 65536, *W3 = b2 + 256, *b3 = W3 + aout * 256;
-      M(l, W1, nullptr, 1 << 30, ob, 0, 0, nat(256), nat(ob), 8, blocks_of(ob), &ad.W1);
-      M(l, W2, nullptr, 1 << 30, 256, 0, 0, nat(256), nat(256), 8, 8, &ad.W2, 1);
-      M(l, W3, nullptr, 1 << 30, 256, 0, 0, nat(aout), nat(256), blocks_of(aout), 8, &ad.Wh, 1);
+      const int l = t == 0 ? PJ_ACTOR : PJ_TARG;
+      const float *W1 = P + L.w(0), *W2 = P + L.w(1), *W3 = P + L.w(2);
+      pp.M(l, W1, nullptr, 1 << 30, ob, 0, 0, nat(256), nat(ob), 8, blocks_of(ob), &ad.W1);
+      pp.M(l, W2, nullptr, 1 << 30, 256, 0, 0, nat(256), nat(256), 8, 8, &ad.W2, 1);
+      pp.M(l, W3, nullptr, 1 << 30, 256, 0, 0, nat(aout), nat(256), blocks_of(aout), 8, &ad.Wh, 1);
       if (t == 0) {
-        M(l, W2, nullptr, 1 << 30, 256, 1, 0, nat(256), nat(256), 8, 8, &ad.W2T, 1);
-        M(l, W3, nullptr, 1 << 30, 256, 1, 0, nat(256), nat(aout), 8, blocks_of(aout), &ad.WhT);
+        pp.M(l, W2, nullptr, 1 << 30, 256, 1, 0, nat(256), nat(256), 8, 8, &ad.W2T, 1);
+        pp.M(l, W3, nullptr, 1 << 30, 256, 1, 0, nat(256), nat(aout), 8, blocks_of(aout), &ad.WhT);
       }
-      ad.tb1 = T(b1, 256);
-      ad.tb2 = T(b2, 256);
-      ad.tbh = T(b3, aout);
+      ad.tb1 = pp.T(P + L.b(0), 256);
+      ad.tb2 = pp.T(P + L.b(1), 256);
+      ad.tbh = pp.T(P + L.b(2), aout);
     }
   }
+  const int in = 2 * ob, nbi = blocks_of(ob) + blocks_of(aout);
   if (!a->ddpg) {
-    // ---- ACM (basic_model.py:108-117): fc1 [64][2ob], fc2 [32][64], fc3 [ac][32]
-    {
-      const float* P = a->net[SPP_NET_ACM].p;
-      const int in = 2 * ob;
-      const float *W1 = P, *b1 = W1 + 64 * in, *W2 = b1 + 64, *b2 = W2 + 32 * 64, *W3 = b2 + 32, *b3 = W3 + ac * 32;
-      M(&a->pj_acm, W1, nullptr, 1 << 30, in, 0, 0, nat(64), cat(ob, aout), 2, blocks_of(ob) + blocks_of(aout),
-        &a->acm.W1);
-      M(&a->pj_acm, W2, nullptr, 1 << 30, 64, 0, 0, nat(32), nat(64), 1, 2, &a->acm.W2);
-      M(&a->pj_acm, W3, nullptr, 1 << 30, 32, 0, 0, nat(ac), nat(32), 1, 1, &a->acm.W3);
-      M(&a->pj_acm, W3, nullptr, 1 << 30, 32, 1, 0, nat(32), nat(ac), 1, 1, &a->acm.W3T);
-      M(&a->pj_acm, W2, nullptr, 1 << 30, 64, 1, 0, nat(64), nat(32), 2, 1, &a->acm.W2T);
-      M(&a->pj_acm, W1, nullptr, 1 << 30, in, 1, ob, nat(aout), nat(64), blocks_of(aout), 2, &a->acm.W1Ta);
-      M(&a->pj_acm, W1, nullptr, 1 << 30, in, 0, 0, nat(64), nat(in), 2, blocks_of(in), &a->acm_W1n);
-      a->acm.tb1 = T(b1, 64);
-      a->acm.tb2 = T(b2, 32);
-      a->acm.tb3 = T(b3, ac);
-    }
-  } else if (!a->plain) {
-    // ---- BasicAcM (acm/models/basic_acm.py:11-21): t, t1, fc1 [100][2ob], fc2 [50][100],
-    //      fc21 [50][2ob], fc3 [ac][50]
+    // ---- ACM: fc1 [64][2ob], fc2 [32][64], fc3 [ac][32]
     const float* P = a->net[SPP_NET_ACM].p;
-    const int in = 2 * ob;
-    const float *t = P, *t1 = P + 1, *W1 = t1 + ac, *b1 = W1 + 100 * in, *W2 = b1 + 100, *b2 = W2 + 50 * 100,
-                *W21 = b2 + 50, *b21 = W21 + 50 * in, *W3 = b21 + 50, *b3 = W3 + ac * 50;
+    const NetLayout& L = a->lay[SPP_NET_ACM];
+    const float *W1 = P + L.w(0), *W2 = P + L.w(1), *W3 = P + L.w(2);
+    pp.M(PJ_ACM, W1, nullptr, 1 << 30, in, 0, 0, nat(64), cat(ob, aout), 2, nbi, &a->acm.W1);
+    pp.M(PJ_ACM, W2, nullptr, 1 << 30, 64, 0, 0, nat(32), nat(64), 1, 2, &a->acm.W2);
+    pp.M(PJ_ACM, W3, nullptr, 1 << 30, 32, 0, 0, nat(ac), nat(32), 1, 1, &a->acm.W3);
+    pp.M(PJ_ACM, W3, nullptr, 1 << 30, 32, 1, 0, nat(32), nat(ac), 1, 1, &a->acm.W3T);
+    pp.M(PJ_ACM, W2, nullptr, 1 << 30, 64, 1, 0, nat(64), nat(32), 2, 1, &a->acm.W2T);
+    pp.M(PJ_ACM, W1, nullptr, 1 << 30, in, 1, ob, nat(aout), nat(64), blocks_of(aout), 2, &a->acm.W1Ta);
+    pp.M(PJ_ACM, W1, nullptr, 1 << 30, in, 0, 0, nat(64), nat(in), 2, blocks_of(in), &a->acm_W1n);
+    a->acm.tb1 = pp.T(P + L.b(0), 64);
+    a->acm.tb2 = pp.T(P + L.b(1), 32);
+    a->acm.tb3 = pp.T(P + L.b(2), ac);
+  } else if (!a->plain) {
+    // ---- BasicAcM: t, t1, fc1 [100][2ob], fc2 [50][100], fc21 [50][2ob], fc3 [ac][50]
+    const float* P = a->net[SPP_NET_ACM].p;
+    const NetLayout& L = a->lay[SPP_NET_ACM];
+    const float *W1 = P + L.w(0), *W2 = P + L.w(1), *W21 = P + L.w(kBacmFc21), *W3 = P + L.w(kBacmFc3);
     BAcmDev& B = a->bacm;
-    const int nbi = blocks_of(ob) + blocks_of(aout);
-    M(&a->pj_acm, W1, nullptr, 1 << 30, in, 0, 0, nat(100), cat(ob, aout), 4, nbi, &B.W1);
-    M(&a->pj_acm, W21, nullptr, 1 << 30, in, 0, 0, nat(50), cat(ob, aout), 2, nbi, &B.W21);
-    M(&a->pj_acm, W2, nullptr, 1 << 30, 100, 0, 0, nat(50), nat(100), 2, 4, &B.W2);
-    M(&a->pj_acm, W3, nullptr, 1 << 30, 50, 0, 0, nat(ac), nat(50), 1, 2, &B.W3);
-    M(&a->pj_acm, W3, nullptr, 1 << 30, 50, 1, 0, nat(50), nat(ac), 2, 1, &B.W3T);
-    M(&a->pj_acm, W2, nullptr, 1 << 30, 100, 1, 0, nat(100), nat(50), 4, 2, &B.W2T);
-    M(&a->pj_acm, W1, nullptr, 1 << 30, in, 1, ob, nat(aout), nat(100), blocks_of(aout), 4, &B.W1Ta);
-    M(&a->pj_acm, W21, nullptr, 1 << 30, in, 1, ob, nat(aout), nat(50), blocks_of(aout), 2, &B.W21Ta);
-    M(&a->pj_acm, W1, nullptr, 1 << 30, in, 0, 0, nat(100), nat(in), 4, blocks_of(in), &a->bacm_W1n);
-    M(&a->pj_acm, W21, nullptr, 1 << 30, in, 0, 0, nat(50), nat(in), 2, blocks_of(in), &a->bacm_W21n);
-    B.tb1 = T(b1, 100);
-    B.tb21 = T(b21, 50);
-    B.tb2 = T(b2, 50);
-    B.tb3 = T(b3, ac);
-    B.t = t;
-    B.t1 = t1;
+    pp.M(PJ_ACM, W1, nullptr, 1 << 30, in, 0, 0, nat(100), cat(ob, aout), 4, nbi, &B.W1);
+    pp.M(PJ_ACM, W21, nullptr, 1 << 30, in, 0, 0, nat(50), cat(ob, aout), 2, nbi, &B.W21);
+    pp.M(PJ_ACM, W2, nullptr, 1 << 30, 100, 0, 0, nat(50), nat(100), 2, 4, &B.W2);
+    pp.M(PJ_ACM, W3, nullptr, 1 << 30, 50, 0, 0, nat(ac), nat(50), 1, 2, &B.W3);
+    pp.M(PJ_ACM, W3, nullptr, 1 << 30, 50, 1, 0, nat(50), nat(ac), 2, 1, &B.W3T);
+    pp.M(PJ_ACM, W2, nullptr, 1 << 30, 100, 1, 0, nat(100), nat(50), 4, 2, &B.W2T);
+    pp.M(PJ_ACM, W1, nullptr, 1 << 30, in, 1, ob, nat(aout), nat(100), blocks_of(aout), 4, &B.W1Ta);
+    pp.M(PJ_ACM, W21, nullptr, 1 << 30, in, 1, ob, nat(aout), nat(50), blocks_of(aout), 2, &B.W21Ta);
+    pp.M(PJ_ACM, W1, nullptr, 1 << 30, in, 0, 0, nat(100), nat(in), 4, blocks_of(in), &a->bacm_W1n);
+    pp.M(PJ_ACM, W21, nullptr, 1 << 30, in, 0, 0, nat(50), nat(in), 2, blocks_of(in), &a->bacm_W21n);
+    B.tb1 = pp.T(P + L.b(0), 100);
+    B.tb21 = pp.T(P + L.b(kBacmFc21), 50);
+    B.tb2 = pp.T(P + L.b(1), 50);
+    B.tb3 = pp.T(P + L.b(kBacmFc3), ac);
+    B.t = P + kBacmT;
+    B.t1 = P + kBacmT1;
   }
-  // ---- critics and targets (sac/models.py:75-91): fc1 [256][cin], fc2, fc3 [1][256]
+  // ---- critics and targets: fc1 [256][cin], fc2, fc3 [1][256]
   for (int t = 0; t < 4; ++t) {
     if (a->ddpg && (t == 1 || t == 3)) continue;  // DDPG: one critic and its target
     const int netid = t < 2 ? SPP_NET_CRITIC1 + t : SPP_NET_CRITIC1_TARG + (t - 2);
     CriticDev& cd = t < 2 ? a->critic[t] : a->targ[t - 2];
     const float* P = a->net[netid].p;
-    const float *W1 = P, *b1 = W1 + 256 * cin, *W2 = b1 + 256, *b2 = W2 + 65536, *w3 = b2 + 256, *b3 = w3 + 256;
-    std::vector<PackJob>* fl = t < 2 ? &a->pj_critic_fwd : &a->pj_targ;
-    M(fl, W1, nullptr, 1 << 30, cin, 0, 0, nat(256), cat(ob, ca), 8, blocks_of(ob) + blocks_of(ca), &cd.W1);
-    M(fl, W2, nullptr, 1 << 30, 256, 0, 0, nat(256), nat(256), 8, 8, &cd.W2, 1);
+    const NetLayout& L = a->lay[netid];
+    const float *W1 = P + L.w(0), *W2 = P + L.w(1);
+    const int fl = t < 2 ? PJ_CRITIC : PJ_TARG;
+    pp.M(fl, W1, nullptr, 1 << 30, cin, 0, 0, nat(256), cat(ob, ca), 8, blocks_of(ob) + blocks_of(ca), &cd.W1);
+    pp.M(fl, W2, nullptr, 1 << 30, 256, 0, 0, nat(256), nat(256), 8, 8, &cd.W2, 1);
     if (t < 2) {
-      M(fl, W2, nullptr, 1 << 30, 256, 1, 0, nat(256), nat(256), 8, 8, &cd.W2T, 1);
-      M(fl, W1, nullptr, 1 << 30, cin, 1, ob, nat(ca), nat(256), blocks_of(ca), 8, &cd.W1Ta, 1);
+      pp.M(fl, W2, nullptr, 1 << 30, 256, 1, 0, nat(256), nat(256), 8, 8, &cd.W2T, 1);
+      pp.M(fl, W1, nullptr, 1 << 30, cin, 1, ob, nat(ca), nat(256), blocks_of(ca), 8, &cd.W1Ta, 1);
     }
-    cd.tb1 = T(b1, 256);
-    cd.tb2 = T(b2, 256);
-    cd.tw3 = T(w3, 256);
-    cd.b3 = b3;
+    cd.tb1 = pp.T(P + L.b(0), 256);
+    cd.tb2 = pp.T(P + L.b(1), 256);
+    cd.tw3 = pp.T(P + L.w(2), 256);
+    cd.b3 = P + L.b(2);
   }
   // + the per-launch limit / normaliser segments appended by make_args
-  a->tab_floats = toff;
+  a->tab = pp.tab;
+  a->tab_floats = pp.toff;
   const int extra = 3 * (int)round_up(aout, 32) + (int)round_up(std::max(ac, 1), 32);
-  SPP_REQUIRE(toff + extra <= kTabMax && (int)a->tab.size() + 4 <= kTabSegs, SPP_E_SHAPE,
-              "LDS table too large (%d floats, %d segments)", toff + extra, (int)a->tab.size() + 4);
-  // allocate images
-  size_t nf4 = 0;
-  for (auto& m : ms) nf4 += (size_t)m.job.NBO * m.job.NBI * 4 * 64;
-  a->pk.release();
-  SPP_CHECK_HIP(a->pk.alloc(nf4));
-  size_t of = 0;
-  for (auto& m : ms) {
-    m.job.dst = a->pk.ptr + of;
-    *m.slot = m.job.dst;
-    of += (size_t)m.job.NBO * m.job.NBI * 4 * 64;
-    m.list->push_back(m.job);
-  }
-  // critics: "all" list = fwd list (already includes transposes)
-  a->pj_critic_all = a->pj_critic_fwd;
-  // device job tables: [actor | acm | targ | critic]
-  std::vector<PackJob> all;
-  a->o_actor = (int)all.size(); all.insert(all.end(), a->pj_actor.begin(), a->pj_actor.end());
-  a->o_acm = (int)all.size(); all.insert(all.end(), a->pj_acm.begin(), a->pj_acm.end());
-  a->o_targ = (int)all.size(); all.insert(all.end(), a->pj_targ.begin(), a->pj_targ.end());
-  a->o_cfwd = (int)all.size(); all.insert(all.end(), a->pj_critic_fwd.begin(), a->pj_critic_fwd.end());
-  a->d_pj.release();
-  SPP_CHECK_HIP(a->d_pj.alloc(all.size()));
-  SPP_CHECK_HIP(hipMemcpy(a->d_pj.ptr, all.data(), sizeof(PackJob) * all.size(), hipMemcpyHostToDevice));
-  return SPP_OK;
+  SPP_REQUIRE(pp.toff + extra <= kTabMax && (int)a->tab.size() + 4 <= kTabSegs, SPP_E_SHAPE,
+              "LDS table too large (%d floats, %d segments)", pp.toff + extra, (int)a->tab.size() + 4);
+  return pp.commit(PJ_LISTS, a->pk, a->d_pj, a->pj, a->o_pj);
 }
 
-static void launch_pack(sppAgent* a, int off, int n, hipStream_t st) {
+// pack job lists [first, last) (adjacent in d_pj)
+static void launch_pack(sppAgent* a, int first, int last, hipStream_t st) {
+  const int off = a->o_pj[first], n = a->o_pj[last] - off;
   if (n > 0) hipLaunchKernelGGL(k_pack_matrix, dim3(64, n), dim3(256), 0, st, (const PackJob*)(a->d_pj.ptr + off));
 }
 
@@ -1203,139 +1197,136 @@ static sppStatus finalize_dw(DwSet& D, std::vector<DwJob>& jobs, int nph, int Bp
   return SPP_OK;
 }
 
+// Append a weight-gradient job dW [N][K0 + K1] (+ db) = A [N][Bp] x [X0 | X1]; rows >= nrow2 of it go to
+// (dW2, db2).  fp32 operands; build_dw marks the bf16 sets' jobs.
+static DwJob& dw_job(std::vector<DwJob>& jobs, int Bp, const float* A, int N, const float* X0, int K0, const float* X1,
+                     int K1, float* dW, float* db, int nrow2 = -1, float* dW2 = nullptr, float* db2 = nullptr) {
+  DwJob j{};
+  j.A = A; j.N = N; j.X0 = X0; j.K0 = K0; j.X1 = X1; j.K1 = K1; j.dW = dW; j.db = db; j.Bp = Bp;
+  j.nrow2 = nrow2 < 0 ? N : nrow2;
+  j.dW2 = dW2; j.db2 = db2;
+  j.slab_stride = round_up((int64_t)N * (K0 + K1) + N, 4);
+  jobs.push_back(j);
+  return jobs.back();
+}
+// The job of layer i of a net with gradient buffer G: delta A x the layer's input X0, or [X0 | X1 (K1 rows)]
+static DwJob& layer_dw(std::vector<DwJob>& jobs, int Bp, float* G, const NetLayout& L, int i, const float* A,
+                       const float* X0, const float* X1 = nullptr, int K1 = 0) {
+  return dw_job(jobs, Bp, A, L.rows(i), X0, L.cols(i) - K1, X1, K1, G + L.w(i), G + L.b(i));
+}
+
+static int phase_grid(sppAgent* a, int Bp) {
+  const int ntiles = Bp / 32;
+  return std::max(1, std::min(cdiv(ntiles, kWavesPerWG), a->num_cu));
+}
+// critic / actor phases: the team kernels (one workgroup per tile; sac_team.h, the vanilla DDPG handles'
+// ddpg_team.h) while the tiles fit one per CU; SPP_SAC_TEAM=0 keeps the one-wave kernels at every batch
+static bool phase_team(sppAgent* a, int Bp) {
+  const bool have = a->ddpg ? a->ks.dcritic_team && a->ks.dactor_team : a->ks.critic_team && a->ks.actor_team;
+  return have && a->team_ok && Bp / 32 <= a->num_cu;
+}
+static int tile_grid(sppAgent* a, int Bp) {
+  return phase_team(a, Bp) ? std::max(1, std::min(Bp / 32, a->num_cu)) : phase_grid(a, Bp);
+}
+// the team critic phase splits each tile's two critics over two workgroups while 2 x tiles fit the CUs
+static int sac_critic_grid(sppAgent* a, int Bp) {
+  const int nt = std::max(1, Bp / 32);
+  return phase_team(a, Bp) && 2 * nt <= a->num_cu ? 2 * nt : tile_grid(a, Bp);
+}
+
+// Critic i's jobs: fc1 (delta1 x [s|a]), fc2 (delta2 x h1), fc3 (dq x h2).  fuse3: the critic-phase kernel
+// computes fc3 itself and writes one [256 | 1] partial per wave, nsplit of them: a reduce-only job, whose index
+// is returned (else -1).
+static int critic_dw(sppAgent* a, std::vector<DwJob>& jobs, int Bp, int i, bool fuse3, int nsplit) {
+  float* G = a->net[SPP_NET_CRITIC1 + i].g;
+  const NetLayout& L = a->lay[SPP_NET_CRITIC1 + i];
+  layer_dw(jobs, Bp, G, L, 0, a->D1[i], a->S, a->cfg.acm_critic ? a->AENV : a->ACT, a->cin - a->cfg.ob);
+  layer_dw(jobs, Bp, G, L, 1, a->D2[i], a->H1[i]);
+  if (!fuse3) {
+    layer_dw(jobs, Bp, G, L, 2, a->DQ[i], a->H2[i]);
+    return -1;
+  }
+  DwJob& f = layer_dw(jobs, Bp, G, L, 2, nullptr, nullptr);
+  f.fused = 1;
+  f.nsplit = nsplit;
+  f.wsplit = 1;
+  return (int)jobs.size() - 1;
+}
+
 // (Re)build a weight-gradient job set for batch size B.
-//   set 0: SAC (phase 0 = both critics, phase 1 = actor); set 1: ACM regression
-static int phase_grid(sppAgent* a, int Bp);
-static int sac_grid(sppAgent* a, int Bp);
-static int sac_critic_grid(sppAgent* a, int Bp);
-static bool sac_team(sppAgent* a, int Bp);
-static bool ddpg_team(sppAgent* a, int Bp);
-static int ddpg_grid(sppAgent* a, int Bp);
+//   set 0: the agent update (phase 0 = the critics, phase 1 = actor); set 1: ACM / BasicAcM regression
 static sppStatus build_dw(sppAgent* a, int set, int B) {
   const int Bp = (int)round_up(B, 32);
-  const int ob = a->cfg.ob, aout = a->cfg.aout, ac = a->cfg.ac;
-  const int ca = a->cfg.acm_critic ? ac : aout, cin = ob + ca;
+  const int aout = a->cfg.aout;
   std::vector<DwJob> jobs;
-  // bf16 SAC kernel sets write these operand arrays as bf16 (op_st, sac.hip)
-  std::vector<const float*> b16;
-  if (a->cfg.mlp_bf16 && !a->ddpg && set == 0)
-    b16 = {a->H1[0], a->H1[1], a->H2[0], a->H2[1], a->D1[0], a->D1[1], a->D2[0], a->D2[1],
-           a->AH1, a->AH2, a->AD1, a->AD2};
-  auto is16 = [&](const float* p) { return p && std::find(b16.begin(), b16.end(), p) != b16.end(); };
-  // rows >= nrow2 of a job go to (dW2, db2)
-  auto J = [&](const float* A, int N, const float* X0, int K0, const float* X1, int K1, float* dW, float* db,
-               int nrow2 = -1, float* dW2 = nullptr, float* db2 = nullptr) {
-    DwJob j{};
-    j.A = A; j.N = N; j.X0 = X0; j.K0 = K0; j.X1 = X1; j.K1 = K1; j.dW = dW; j.db = db; j.Bp = Bp;
-    j.nrow2 = nrow2 < 0 ? N : nrow2;
-    j.dW2 = dW2; j.db2 = db2;
-    j.slab_stride = round_up((int64_t)N * (K0 + K1) + N, 4);
-    j.bf16 = a->cfg.mlp_bf16 ? 1 : 0;
-    j.a_bf = is16(A) ? 1 : 0;
-    j.x_bf = is16(X0) ? 1 : 0;
-    jobs.push_back(j);  // (an X1 segment is always staged fp32 input, like X0)
-  };
   DwSet& D = a->dws[set];
-  int nph = 0;
-  if (a->ddpg) {
-    if (set == 0) {
-      // critic phase (ddpg_acm.py:174-185): fc1 (delta1 x [s|a]), fc2 (delta2 x h1), fc3 (dq x h2)
-      float* G = a->net[SPP_NET_CRITIC1].g;
-      float *gW1 = G, *gb1 = gW1 + 256 * cin, *gW2 = gb1 + 256, *gb2 = gW2 + 65536, *gw3 = gb2 + 256, *gb3 = gw3 + 256;
-      J(a->D1[0], 256, a->S, ob, a->cfg.acm_critic ? a->AENV : a->ACT, ca, gW1, gb1);
-      J(a->D2[0], 256, a->H1[0], 256, nullptr, 0, gW2, gb2);
-      int fused0 = -1;
-      if (ob <= 32) {  // fc3: fused into k_ddpg_critic_phase (reduce only; its kFuse3)
-        J(nullptr, 1, nullptr, 256, nullptr, 0, gw3, gb3);
-        jobs.back().fused = 1;
-        jobs.back().nsplit = ddpg_grid(a, Bp) * (ddpg_team(a, Bp) ? kTeamDCritic : kWavesPerWG);
-        jobs.back().wsplit = 1;
-        fused0 = (int)jobs.size() - 1;
-      } else {
-        J(a->DQ[0], 1, a->H2[0], 256, nullptr, 0, gw3, gb3);
-      }
-      D.j0[0] = 0;
-      D.nj[0] = (int)jobs.size();
-      // actor phase (:187-196): fc1 (delta1 x s), fc2 (delta2 x h1), fc3 (dhead x h2)
-      float* A = a->net[SPP_NET_ACTOR].g;
-      float *aW1 = A, *ab1 = aW1 + 256 * ob, *aW2 = ab1 + 256, *ab2 = aW2 + 65536, *aW3 = ab2 + 256,
-            *ab3 = aW3 + aout * 256;
-      J(a->AD1, 256, a->S, ob, nullptr, 0, aW1, ab1);
-      J(a->AD2, 256, a->AH1, 256, nullptr, 0, aW2, ab2);
-      J(a->ADH, aout, a->AH2, 256, nullptr, 0, aW3, ab3);
-      D.j0[1] = D.nj[0];
-      D.nj[1] = (int)jobs.size() - D.nj[0];
-      nph = 2;
-      sppStatus s = finalize_dw(D, jobs, nph, Bp, B, a->num_cu);
-      a->w3p[0] = a->w3p[1] = fused0 >= 0 ? jobs[fused0].slab : nullptr;
-      a->w3p_stride = fused0 >= 0 ? jobs[fused0].slab_stride : 0;
-      return s;
-    } else {
-      SPP_REQUIRE(!a->plain, SPP_E_STATE, "vanilla DDPG has no ACM to regress");
-      // BasicAcM regression (acm.py:246-258): fc1, fc2, fc21 (grad of its output = t * dz), fc3;
-      // t / t1 come from the per-tile partials (k_finalize_bacm)
-      float* G = a->net[SPP_NET_ACM].g;
-      const int in = 2 * ob;
-      float *gW1 = G + 1 + ac, *gb1 = gW1 + 100 * in, *gW2 = gb1 + 100, *gb2 = gW2 + 50 * 100, *gW21 = gb2 + 50,
-            *gb21 = gW21 + 50 * in, *gW3 = gb21 + 50, *gb3 = gW3 + ac * 50;
-      J(a->RBP1, 100, a->RX, in, nullptr, 0, gW1, gb1);
-      J(a->RPZ, 50, a->RBH, 100, nullptr, 0, gW2, gb2);
-      J(a->RPZ21, 50, a->RX, in, nullptr, 0, gW21, gb21);
-      J(a->RP3, ac, a->RBH1, 50, nullptr, 0, gW3, gb3);
-      D.j0[0] = 0;
-      D.nj[0] = (int)jobs.size();
-      nph = 1;
-    }
-  } else if (set == 0) {
-    // critic phase: fc1 (delta1 x [s|a]), fc2 (delta2 x h1) per critic; fc3 (dq x h2) is fused into the
-    // critic-phase kernel, which writes one [256 | 1] partial per wave: a reduce-only job
-    // (bf16 sets with SPP_BF16_FUSE3 = 0: the critic phase stores h2 (bf16) and dq; fc3 is a k_dw job)
-    const bool fuse3 = !a->cfg.mlp_bf16 || SPP_BF16_FUSE3;
-    int fused_idx[2] = {-1, -1};
-    for (int i = 0; i < 2; ++i) {
-      float* G = a->net[SPP_NET_CRITIC1 + i].g;
-      float *gW1 = G, *gb1 = gW1 + 256 * cin, *gW2 = gb1 + 256, *gb2 = gW2 + 65536, *gw3 = gb2 + 256, *gb3 = gw3 + 256;
-      J(a->D1[i], 256, a->S, ob, a->cfg.acm_critic ? a->AENV : a->ACT, ca, gW1, gb1);
-      J(a->D2[i], 256, a->H1[i], 256, nullptr, 0, gW2, gb2);
-      if (!fuse3) {
-        J(a->DQ[i], 1, a->H2[i], 256, nullptr, 0, gw3, gb3);
-        continue;
-      }
-      J(nullptr, 1, nullptr, 256, nullptr, 0, gw3, gb3);
-      jobs.back().fused = 1;
-      jobs.back().nsplit = sac_critic_grid(a, Bp) * (sac_team(a, Bp) ? kTeamCritic : kWavesPerWG);
-      jobs.back().wsplit = 1;
-      fused_idx[i] = (int)jobs.size() - 1;
-    }
+  int nph = 1, fused[2] = {-1, -1};
+  if (set == 0) {
+    // critic phase.  fc3 is fused on the SAC sets (bf16 sets with SPP_BF16_FUSE3 = 0: the critic phase stores
+    // h2 (bf16) and dq; fc3 is a k_dw job) and on the DDPG sets with ob <= 32 (k_ddpg_critic_phase's kFuse3)
+    const bool team = phase_team(a, Bp);
+    const bool fuse3 = a->ddpg ? a->cfg.ob <= 32 : (!a->cfg.mlp_bf16 || SPP_BF16_FUSE3);
+    const int nsplit = a->ddpg ? tile_grid(a, Bp) * (team ? kTeamDCritic : kWavesPerWG)
+                               : sac_critic_grid(a, Bp) * (team ? kTeamCritic : kWavesPerWG);
+    for (int i = 0; i < (a->ddpg ? 1 : 2); ++i) fused[i] = critic_dw(a, jobs, Bp, i, fuse3, nsplit);
     D.j0[0] = 0;
     D.nj[0] = (int)jobs.size();
+    // actor phase: fc1 (delta1 x s), fc2 (delta2 x h1), head (dhead x h2): DDPG's fc3, SAC's [mu | log-std] pair
     float* G = a->net[SPP_NET_ACTOR].g;
-    float *gW1 = G, *gb1 = gW1 + 256 * ob, *gW2 = gb1 + 256, *gb2 = gW2 + 65536, *gWp = gb2 + 256,
-          *gbp = gWp + aout * 256, *gWs = gbp + aout, *gbs = gWs + aout * 256;
-    J(a->AD1, 256, a->S, ob, nullptr, 0, gW1, gb1);
-    J(a->AD2, 256, a->AH1, 256, nullptr, 0, gW2, gb2);
-    J(a->ADH, 2 * aout, a->AH2, 256, nullptr, 0, gWp, gbp, aout, gWs, gbs);  // [mu | log-std] heads
+    const NetLayout& L = a->lay[SPP_NET_ACTOR];
+    layer_dw(jobs, Bp, G, L, 0, a->AD1, a->S);
+    layer_dw(jobs, Bp, G, L, 1, a->AD2, a->AH1);
+    if (a->ddpg)
+      layer_dw(jobs, Bp, G, L, 2, a->ADH, a->AH2);
+    else
+      dw_job(jobs, Bp, a->ADH, 2 * aout, a->AH2, L.cols(kFcProb), nullptr, 0, G + L.w(kFcProb), G + L.b(kFcProb), aout,
+             G + L.w(kFcScale), G + L.b(kFcScale));
     D.j0[1] = D.nj[0];
     D.nj[1] = (int)jobs.size() - D.nj[0];
     nph = 2;
-    sppStatus s = finalize_dw(D, jobs, nph, Bp, B, a->num_cu);
-    for (int i = 0; i < 2; ++i) a->w3p[i] = fuse3 ? jobs[fused_idx[i]].slab : nullptr;
-    a->w3p_stride = fuse3 ? jobs[fused_idx[0]].slab_stride : 0;
-    return s;
   } else {
     float* G = a->net[SPP_NET_ACM].g;
-    const int in = 2 * ob;
-    float *gW1 = G, *gb1 = gW1 + 64 * in, *gW2 = gb1 + 64, *gb2 = gW2 + 32 * 64, *gW3 = gb2 + 32, *gb3 = gW3 + ac * 32;
-    J(a->RP1, 64, a->RX, in, nullptr, 0, gW1, gb1);
-    J(a->RP2, 32, a->RZ1, 64, nullptr, 0, gW2, gb2);
-    J(a->RP3, ac, a->RZ2, 32, nullptr, 0, gW3, gb3);
+    const NetLayout& L = a->lay[SPP_NET_ACM];
+    if (a->ddpg) {
+      SPP_REQUIRE(!a->plain, SPP_E_STATE, "vanilla DDPG has no ACM to regress");
+      // BasicAcM regression (acm.py:246-258): fc1, fc2, fc21 (grad of its output = t * dz), fc3;
+      // t / t1 come from the per-tile partials (k_finalize_bacm)
+      layer_dw(jobs, Bp, G, L, 0, a->RBP1, a->RX);
+      layer_dw(jobs, Bp, G, L, 1, a->RPZ, a->RBH);
+      layer_dw(jobs, Bp, G, L, kBacmFc21, a->RPZ21, a->RX);
+      layer_dw(jobs, Bp, G, L, kBacmFc3, a->RP3, a->RBH1);
+    } else {
+      layer_dw(jobs, Bp, G, L, 0, a->RP1, a->RX);
+      layer_dw(jobs, Bp, G, L, 1, a->RP2, a->RZ1);
+      layer_dw(jobs, Bp, G, L, 2, a->RP3, a->RZ2);
+    }
     D.j0[0] = 0;
     D.nj[0] = (int)jobs.size();
-    nph = 1;
   }
-  return finalize_dw(D, jobs, nph, Bp, B, a->num_cu);
+  if (a->cfg.mlp_bf16) {
+    // bf16 SAC kernel sets write these operand arrays as bf16 (op_st, sac.hip); an X1 segment is always
+    // staged fp32 input, like a fp32 X0
+    std::vector<const float*> b16;
+    if (!a->ddpg && set == 0)
+      b16 = {a->H1[0], a->H1[1], a->H2[0], a->H2[1], a->D1[0], a->D1[1], a->D2[0], a->D2[1],
+             a->AH1, a->AH2, a->AD1, a->AD2};
+    auto is16 = [&](const float* p) { return p && std::find(b16.begin(), b16.end(), p) != b16.end(); };
+    for (DwJob& j : jobs) {
+      j.bf16 = 1;
+      j.a_bf = is16(j.A) ? 1 : 0;
+      j.x_bf = is16(j.X0) ? 1 : 0;
+    }
+  }
+  const sppStatus s = finalize_dw(D, jobs, nph, Bp, B, a->num_cu);
+  if (set == 0) {  // the critics' fused fc3 partials (DDPG: one critic)
+    for (int i = 0; i < 2; ++i) {
+      const int f = fused[a->ddpg ? 0 : i];
+      a->w3p[i] = f >= 0 ? jobs[f].slab : nullptr;
+    }
+    a->w3p_stride = fused[0] >= 0 ? jobs[fused[0]].slab_stride : 0;
+  }
+  return s;
 }
-
 
 static void launch_dw_set(DwSet& D, int ph, hipStream_t st) {
   const int* ij = D.items.ptr + D.ioff[ph];
@@ -1416,32 +1407,6 @@ static SacArgs make_args(sppAgent* a, int B) {
   return p;
 }
 
-static int phase_grid(sppAgent* a, int Bp) {
-  const int ntiles = Bp / 32;
-  return std::max(1, std::min(cdiv(ntiles, kWavesPerWG), a->num_cu));
-}
-// SAC phases: the team kernels (one workgroup per tile, sac_team.h) while the tiles fit one per CU
-static bool sac_team(sppAgent* a, int Bp) {
-  return a->ks.critic_team && a->ks.actor_team && a->team_ok && Bp / 32 <= a->num_cu;
-}
-static int sac_grid(sppAgent* a, int Bp) {
-  return sac_team(a, Bp) ? std::max(1, std::min(Bp / 32, a->num_cu)) : phase_grid(a, Bp);
-}
-// the team critic phase splits each tile's two critics over two workgroups while 2 x tiles fit the CUs
-static int sac_critic_grid(sppAgent* a, int Bp) {
-  const int nt = std::max(1, Bp / 32);
-  return sac_team(a, Bp) && 2 * nt <= a->num_cu ? 2 * nt : sac_grid(a, Bp);
-}
-
-// DDPG phases of the vanilla handles: the team kernels (one workgroup per tile, ddpg_team.h) while the tiles
-// fit one per CU; SPP_SAC_TEAM=0 keeps the one-wave kernels at every batch
-static bool ddpg_team(sppAgent* a, int Bp) {
-  return a->ks.dcritic_team && a->ks.dactor_team && a->team_ok && Bp / 32 <= a->num_cu;
-}
-static int ddpg_grid(sppAgent* a, int Bp) {
-  return ddpg_team(a, Bp) ? std::max(1, std::min(Bp / 32, a->num_cu)) : phase_grid(a, Bp);
-}
-
 static sppStatus check_ready(sppAgent* a) {
   SPP_REQUIRE(a->ddpg || (a->alpha_state && a->alpha_f32), SPP_E_STATE, "alpha not bound");
   SPP_REQUIRE(a->cfg.min_max_denormalize ? (a->lo && a->hi) : (a->mean && a->std), SPP_E_STATE,
@@ -1492,11 +1457,12 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
   a->ddpg = cfg->algo == SPP_ALGO_DDPG_ACM || cfg->algo == SPP_ALGO_DDPG;
   a->plain = cfg->algo == SPP_ALGO_SAC || cfg->algo == SPP_ALGO_DDPG;
   const bool dd = a->ddpg;
-  a->nsize[SPP_NET_ACTOR] = dd ? ddpg_actor_size(ob, aout) : sac_actor_size(ob, aout);
-  a->nsize[SPP_NET_ACTOR_TARG] = dd ? ddpg_actor_size(ob, aout) : 0;
-  a->nsize[SPP_NET_CRITIC1] = a->nsize[SPP_NET_CRITIC1_TARG] = critic_size(a->cin);
-  a->nsize[SPP_NET_CRITIC2] = a->nsize[SPP_NET_CRITIC2_TARG] = dd ? 0 : critic_size(a->cin);
-  a->nsize[SPP_NET_ACM] = dd ? (a->plain ? 0 : bacm_size(2 * ob, ac)) : acm_size(2 * ob, ac);
+  a->lay[SPP_NET_ACTOR] = dd ? ddpg_actor_layout(ob, aout) : sac_actor_layout(ob, aout);
+  if (dd) a->lay[SPP_NET_ACTOR_TARG] = a->lay[SPP_NET_ACTOR];
+  a->lay[SPP_NET_CRITIC1] = a->lay[SPP_NET_CRITIC1_TARG] = critic_layout(a->cin);
+  if (!dd) a->lay[SPP_NET_CRITIC2] = a->lay[SPP_NET_CRITIC2_TARG] = critic_layout(a->cin);
+  if (!dd) a->lay[SPP_NET_ACM] = acm_layout(2 * ob, ac);
+  else if (!a->plain) a->lay[SPP_NET_ACM] = bacm_layout(2 * ob, ac);
   a->Bmax = cfg->max_batch;
   const int64_t Bp = round_up(cfg->max_batch, 32);
   SPP_REQUIRE((int64_t)Bp * 256 * 4 < ((int64_t)1 << 31), SPP_E_SHAPE, "max_batch %d too large (31-bit buffer offsets)",
@@ -1589,7 +1555,7 @@ sppStatus sppAgentDestroy(sppAgentHandle a) {
 
 sppStatus sppAgentNetSize(sppAgentHandle a, int net, int64_t* n) {
   SPP_REQUIRE(a && n && net >= 0 && net < SPP_NET_COUNT, SPP_E_INVALID_ARG, "bad net id");
-  *n = a->nsize[net];
+  *n = a->lay[net].size();
   return SPP_OK;
 }
 
@@ -1598,10 +1564,10 @@ sppStatus sppAgentBindNet(sppAgentHandle a, int net, float* p, float* g, float* 
   const bool trainable = net == SPP_NET_ACTOR || net == SPP_NET_CRITIC1 || net == SPP_NET_CRITIC2 || net == SPP_NET_ACM;
   SPP_REQUIRE(!trainable || (g && m && v), SPP_E_INVALID_ARG, "bind: trainable net %d needs grad/m/v", net);
   const bool changed = a->net[net].p != p || a->net[net].g != g;
-  a->net[net] = NetBufs{p, g, m, v, a->nsize[net]};
+  a->net[net] = NetBufs{p, g, m, v, a->lay[net].size()};
   if (changed) {  // pack tables and gradient jobs hold these pointers
     a->pk.release();
-    a->pj_actor.clear(); a->pj_acm.clear(); a->pj_targ.clear(); a->pj_critic_fwd.clear(); a->pj_critic_all.clear();
+    a->pj.clear();
     a->tab.clear();
   }
   return SPP_OK;
@@ -1675,12 +1641,11 @@ static sppStatus critic_grads_staged(sppAgentHandle a, float* losses, hipStream_
     if (s) return s;
   }
   // pack actor, ACM, targets, critics (current weights)
-  launch_pack(a, a->o_actor, (int)(a->pj_actor.size() + a->pj_acm.size() + a->pj_targ.size() + a->pj_critic_fwd.size()),
-              st);
+  launch_pack(a, PJ_ACTOR, PJ_LISTS, st);
   SacArgs p = make_args(a, B);
   const int grid = sac_critic_grid(a, p.Bp);
   tmark(a, 0, st);
-  const bool team = sac_team(a, p.Bp);
+  const bool team = phase_team(a, p.Bp);
   hipLaunchKernelGGL(team ? a->ks.critic_team : a->ks.critic, dim3(grid), dim3(team ? 64 * kTeamCritic : 256), 0, st, p);
   tmark(a, 0, st);
   SPP_CHECK_HIP(hipGetLastError());
@@ -1722,12 +1687,12 @@ static sppStatus actor_grads(sppAgentHandle a, float* losses, hipStream_t st) {
   const int B = a->cur_B;
   SPP_REQUIRE(B > 0, SPP_E_STATE, "no staged batch");
   // repack the updated critics
-  launch_pack(a, a->o_cfwd, (int)a->pj_critic_fwd.size(), st);
+  launch_pack(a, PJ_CRITIC, PJ_LISTS, st);
   SacArgs p = make_args(a, B);
   AcmScratch z{a->Z1, a->Z2, a->T3, a->GAD, a->MASK};
-  const int grid = sac_grid(a, p.Bp);
+  const int grid = tile_grid(a, p.Bp);
   tmark(a, 1, st);
-  const bool team = sac_team(a, p.Bp);
+  const bool team = phase_team(a, p.Bp);
   if (!team && a->minq_split) {
     // min-critic split: forward to q = min(Q1, Q2); the two lists of samples by chosen critic; that critic's
     // backward over the regrouped samples; everything behind it in the original order (sac.hip)
@@ -1798,9 +1763,8 @@ static std::vector<PackJob> images_of(sppAgent* a, int net) {
   std::vector<PackJob> out;
   const NetBufs& nb = a->net[net];
   if (!nb.p) return out;
-  for (auto* l : {&a->pj_actor, &a->pj_acm, &a->pj_targ, &a->pj_critic_fwd})
-    for (const PackJob& j : *l)
-      if (j.W >= nb.p && j.W < nb.p + nb.n) out.push_back(j);
+  for (const PackJob& j : a->pj)
+    if (j.W >= nb.p && j.W < nb.p + nb.n) out.push_back(j);
   return out;
 }
 
@@ -1882,12 +1846,11 @@ sppStatus sppDdpgAcmCriticGrads(sppAgentHandle a, const sppBatch* bt, float* los
   SPP_REQUIRE(B > 0, SPP_E_STATE, "no staged batch");
   if ((s = check_ready(a))) return s;
   if (a->dws[0].B != B && (s = build_dw(a, 0, B))) return s;
-  launch_pack(a, a->o_actor, (int)(a->pj_actor.size() + a->pj_acm.size() + a->pj_targ.size() + a->pj_critic_fwd.size()),
-              st);
+  launch_pack(a, PJ_ACTOR, PJ_LISTS, st);
   SacArgs p = make_args(a, B);
   tmark(a, 0, st);
-  const bool team = ddpg_team(a, p.Bp);
-  hipLaunchKernelGGL(team ? a->ks.dcritic_team : a->ks.dcritic, dim3(ddpg_grid(a, p.Bp)),
+  const bool team = phase_team(a, p.Bp);
+  hipLaunchKernelGGL(team ? a->ks.dcritic_team : a->ks.dcritic, dim3(tile_grid(a, p.Bp)),
                      dim3(team ? 64 * kTeamDCritic : 256), 0, st, p, a->bz);
   tmark(a, 0, st);
   SPP_CHECK_HIP(hipGetLastError());
@@ -1913,11 +1876,11 @@ sppStatus sppDdpgAcmActorGrads(sppAgentHandle a, float* losses, void* stream) {
   SPP_REQUIRE(a && a->ddpg && a->cur_B > 0, SPP_E_STATE, "DDPG_AcM agent: no staged batch");
   hipStream_t st = S(stream);
   const int B = a->cur_B;
-  launch_pack(a, a->o_cfwd, (int)a->pj_critic_fwd.size(), st);  // the updated critic
+  launch_pack(a, PJ_CRITIC, PJ_LISTS, st);  // the updated critic
   SacArgs p = make_args(a, B);
   tmark(a, 1, st);
-  const bool team = ddpg_team(a, p.Bp);
-  hipLaunchKernelGGL(team ? a->ks.dactor_team : a->ks.dactor, dim3(ddpg_grid(a, p.Bp)),
+  const bool team = phase_team(a, p.Bp);
+  hipLaunchKernelGGL(team ? a->ks.dactor_team : a->ks.dactor, dim3(tile_grid(a, p.Bp)),
                      dim3(team ? 64 * kTeamDActor : 256), 0, st, p, a->bz);
   tmark(a, 1, st);
   SPP_CHECK_HIP(hipGetLastError());
@@ -2008,7 +1971,7 @@ sppStatus sppAcmRegressGrads(sppAgentHandle a, const float* x, const float* y, i
   if (a->dws[1].B != B) {
     if ((s = build_dw(a, 1, B))) return s;
   }
-  launch_pack(a, a->o_acm, (int)a->pj_acm.size(), st);
+  launch_pack(a, PJ_ACM, PJ_TARG, st);
   SacArgs p = make_args(a, B);
   if (a->ddpg) {  // BasicAcM: natural-input fc1 / fc21 packings
     p.bacm.W1 = a->bacm_W1n;
@@ -2236,7 +2199,7 @@ sppStatus sppPolicyAct(sppAgentHandle a, const float* obs, int E, const float* e
   hipStream_t st = S(stream);
   sppStatus s = check_ready(a);
   if (s) return s;
-  launch_pack(a, a->o_actor, (int)(a->pj_actor.size() + a->pj_acm.size()), st);
+  launch_pack(a, PJ_ACTOR, PJ_TARG, st);
   SacArgs p = make_args(a, 32);
   ActArgs g{E, mode, denorm_out, act_noise, obs, eps, noise, target_out, env_out, a->plain ? 1 : 0};
   const int grid = std::max(1, std::min(cdiv(cdiv(E, 32), kWavesPerWG), a->num_cu));
@@ -2317,8 +2280,6 @@ static bool find_onp(int ob, int aout, OnpKernels* k) {
   if (ob == 3 && aout == 1) { *k = make_onp<3, 1>(); return true; }      // Pendulum (tests)
   return false;
 }
-static int64_t onp_actor_size(int ob, int aout) { return aout + 64LL * ob + 64 + 64 * 64 + 64 + aout * 64LL + aout; }
-static int64_t onp_critic_size(int ob) { return 64LL * ob + 64 + 64 * 64 + 64 + 64 + 1; }
 }  // namespace spp
 
 struct sppOnPolicy {
@@ -2326,12 +2287,12 @@ struct sppOnPolicy {
   int device = 0, num_cu = 256;
   OnpKernels ks{};
   NetBufs net[2];  // 0 actor, 1 critic
-  int64_t nsize[2] = {};
+  NetLayout lay[2];
   int64_t steps[2] = {0, 0};
   DevArray<float> lim;
   DevArray<float4> pk;
   DevArray<PackJob> d_pj;
-  int npj_actor = 0, npj_critic = 0;
+  int o_pj[3] = {};  // pack jobs in d_pj: the actor's [o_pj[0], o_pj[1]), the critic's [o_pj[1], o_pj[2])
   OnpNet actor{}, critic{};
   std::vector<TabSeg> tab;
   DevArray<float> scratch;
@@ -2350,60 +2311,37 @@ struct sppOnPolicy {
 static sppStatus onp_packs(sppOnPolicy* o) {
   const int ob = o->cfg.ob, aout = o->cfg.aout;
   SPP_REQUIRE(o->net[0].p && o->net[1].p, SPP_E_STATE, "on-policy nets not bound");
-  std::vector<PackJob> jobs;
-  std::vector<const float4**> slots;
-  auto M = [&](const float* W, int ld, int trans, MapDesc out, MapDesc in, int NBO, int NBI, const float4** slot) {
-    jobs.push_back(PackJob{W, nullptr, 1 << 30, ld, trans, 0, out, in, NBO, NBI, 0, nullptr});
-    slots.push_back(slot);
-  };
-  o->tab.clear();
-  int toff = 0;
-  auto T = [&](const float* v, int n) {
-    const int off = toff, tot = (int)round_up(n, 32);
-    o->tab.push_back(TabSeg{v, n, tot, off, 0});
-    toff += tot;
-    return off;
-  };
-  {  // actor: log_scale, fc1, fc2, fc3 (basic_model.py:14-21)
+  PackPlan pp;
+  {  // actor (list 0): log_scale, fc1, fc2, fc3
     const float* P = o->net[0].p;
-    const float *W1 = P + aout, *b1 = W1 + 64 * ob, *W2 = b1 + 64, *b2 = W2 + 64 * 64, *W3 = b2 + 64,
-                *b3 = W3 + aout * 64;
-    M(W1, ob, 0, nat(64), nat(ob), 2, blocks_of(ob), &o->actor.W1);
-    M(W2, 64, 0, nat(64), nat(64), 2, 2, &o->actor.W2);
-    M(W3, 64, 0, nat(aout), nat(64), blocks_of(aout), 2, &o->actor.W3);
-    M(W3, 64, 1, nat(64), nat(aout), 2, blocks_of(aout), &o->actor.W3T);
-    M(W2, 64, 1, nat(64), nat(64), 2, 2, &o->actor.W2T);
-    o->actor.tb1 = T(b1, 64);
-    o->actor.tb2 = T(b2, 64);
-    o->actor.tb3 = T(b3, aout);
+    const NetLayout& L = o->lay[0];
+    const float *W1 = P + L.w(0), *W2 = P + L.w(1), *W3 = P + L.w(2);
+    pp.M(0, W1, nullptr, 1 << 30, ob, 0, 0, nat(64), nat(ob), 2, blocks_of(ob), &o->actor.W1);
+    pp.M(0, W2, nullptr, 1 << 30, 64, 0, 0, nat(64), nat(64), 2, 2, &o->actor.W2);
+    pp.M(0, W3, nullptr, 1 << 30, 64, 0, 0, nat(aout), nat(64), blocks_of(aout), 2, &o->actor.W3);
+    pp.M(0, W3, nullptr, 1 << 30, 64, 1, 0, nat(64), nat(aout), 2, blocks_of(aout), &o->actor.W3T);
+    pp.M(0, W2, nullptr, 1 << 30, 64, 1, 0, nat(64), nat(64), 2, 2, &o->actor.W2T);
+    o->actor.tb1 = pp.T(P + L.b(0), 64);
+    o->actor.tb2 = pp.T(P + L.b(1), 64);
+    o->actor.tb3 = pp.T(P + L.b(2), aout);
   }
-  o->npj_actor = (int)jobs.size();
-  {  // critic: fc1, fc2, fc3 (basic_model.py:62-70)
+  {  // critic (list 1): fc1, fc2, fc3
     const float* P = o->net[1].p;
-    const float *W1 = P, *b1 = W1 + 64 * ob, *W2 = b1 + 64, *b2 = W2 + 64 * 64, *w3 = b2 + 64, *b3 = w3 + 64;
-    M(W1, ob, 0, nat(64), nat(ob), 2, blocks_of(ob), &o->critic.W1);
-    M(W2, 64, 0, nat(64), nat(64), 2, 2, &o->critic.W2);
-    M(W2, 64, 1, nat(64), nat(64), 2, 2, &o->critic.W2T);
-    o->critic.tb1 = T(b1, 64);
-    o->critic.tb2 = T(b2, 64);
-    o->critic.tb3 = T(w3, 64);
-    o->critic.b3 = b3;
+    const NetLayout& L = o->lay[1];
+    const float *W1 = P + L.w(0), *W2 = P + L.w(1);
+    pp.M(1, W1, nullptr, 1 << 30, ob, 0, 0, nat(64), nat(ob), 2, blocks_of(ob), &o->critic.W1);
+    pp.M(1, W2, nullptr, 1 << 30, 64, 0, 0, nat(64), nat(64), 2, 2, &o->critic.W2);
+    pp.M(1, W2, nullptr, 1 << 30, 64, 1, 0, nat(64), nat(64), 2, 2, &o->critic.W2T);
+    o->critic.tb1 = pp.T(P + L.b(0), 64);
+    o->critic.tb2 = pp.T(P + L.b(1), 64);
+    o->critic.tb3 = pp.T(P + L.w(2), 64);
+    o->critic.b3 = P + L.b(2);
   }
-  o->npj_critic = (int)jobs.size() - o->npj_actor;
-  SPP_REQUIRE(toff <= 1024 && o->tab.size() <= 8, SPP_E_SHAPE, "on-policy LDS table too large");
-  size_t nf4 = 0;
-  for (auto& j : jobs) nf4 += (size_t)j.NBO * j.NBI * 256;
-  o->pk.release();
-  SPP_CHECK_HIP(o->pk.alloc(nf4));
-  size_t of = 0;
-  for (size_t i = 0; i < jobs.size(); ++i) {
-    jobs[i].dst = o->pk.ptr + of;
-    *slots[i] = jobs[i].dst;
-    of += (size_t)jobs[i].NBO * jobs[i].NBI * 256;
-  }
-  o->d_pj.release();
-  SPP_CHECK_HIP(o->d_pj.alloc(jobs.size()));
-  SPP_CHECK_HIP(hipMemcpy(o->d_pj.ptr, jobs.data(), sizeof(PackJob) * jobs.size(), hipMemcpyHostToDevice));
+  o->tab = pp.tab;
+  SPP_REQUIRE(pp.toff <= 1024 && o->tab.size() <= 8, SPP_E_SHAPE, "on-policy LDS table too large");
+  std::vector<PackJob> jobs;
+  sppStatus s = pp.commit(2, o->pk, o->d_pj, jobs, o->o_pj);
+  if (s) return s;
   AdamJob aj[2] = {AdamJob{o->net[0].p, o->net[0].g, o->net[0].m, o->net[0].v, nullptr, o->net[0].n},
                    AdamJob{o->net[1].p, o->net[1].g, o->net[1].m, o->net[1].v, nullptr, o->net[1].n}};
   if (!o->d_adam.ptr) SPP_CHECK_HIP(o->d_adam.alloc(2));
@@ -2412,29 +2350,15 @@ static sppStatus onp_packs(sppOnPolicy* o) {
   return SPP_OK;
 }
 
+// job set 0: the critic's (net 1), 1: the actor's (net 0); fc1 (delta1 x x), fc2 (delta2 x h1), fc3 (delta3 x h2)
 static sppStatus onp_dw(sppOnPolicy* o, int which, int N) {
-  const int Bp = (int)round_up(N, 32), ob = o->cfg.ob, aout = o->cfg.aout;
+  const int Bp = (int)round_up(N, 32), net = which == 0 ? 1 : 0;
   std::vector<DwJob> jobs;
-  auto J = [&](const float* A, int Nn, const float* X, int K, float* dW, float* db) {
-    DwJob j{};
-    j.A = A; j.N = Nn; j.X0 = X; j.K0 = K; j.dW = dW; j.db = db; j.Bp = Bp; j.nrow2 = Nn;
-    j.slab_stride = round_up((int64_t)Nn * K + Nn, 4);
-    jobs.push_back(j);
-  };
-  if (which == 0) {
-    float* G = o->net[1].g;
-    float *gW1 = G, *gb1 = gW1 + 64 * ob, *gW2 = gb1 + 64, *gb2 = gW2 + 64 * 64, *gw3 = gb2 + 64, *gb3 = gw3 + 64;
-    J(o->D1, 64, o->XT, ob, gW1, gb1);
-    J(o->D2, 64, o->H1, 64, gW2, gb2);
-    J(o->D3, 1, o->H2, 64, gw3, gb3);
-  } else {
-    float* G = o->net[0].g;
-    float *gW1 = G + aout, *gb1 = gW1 + 64 * ob, *gW2 = gb1 + 64, *gb2 = gW2 + 64 * 64, *gW3 = gb2 + 64,
-          *gb3 = gW3 + aout * 64;
-    J(o->D1, 64, o->XT, ob, gW1, gb1);
-    J(o->D2, 64, o->H1, 64, gW2, gb2);
-    J(o->D3, aout, o->H2, 64, gW3, gb3);
-  }
+  float* G = o->net[net].g;
+  const NetLayout& L = o->lay[net];
+  layer_dw(jobs, Bp, G, L, 0, o->D1, o->XT);
+  layer_dw(jobs, Bp, G, L, 1, o->D2, o->H1);
+  layer_dw(jobs, Bp, G, L, 2, o->D3, o->H2);
   DwSet& D = o->dw[which];
   D.j0[0] = 0;
   D.nj[0] = (int)jobs.size();
@@ -2467,8 +2391,8 @@ static sppStatus onp_ready(sppOnPolicy* o, int N, hipStream_t st, int net) {
     sppStatus s = onp_packs(o);
     if (s) return s;
   }
-  const PackJob* pj = (const PackJob*)o->d_pj.ptr + (net == 0 ? 0 : o->npj_actor);
-  hipLaunchKernelGGL(k_pack_matrix, dim3(16, net == 0 ? o->npj_actor : o->npj_critic), dim3(256), 0, st, pj);
+  const PackJob* pj = (const PackJob*)o->d_pj.ptr + o->o_pj[net];
+  hipLaunchKernelGGL(k_pack_matrix, dim3(16, o->o_pj[net + 1] - o->o_pj[net]), dim3(256), 0, st, pj);
   return SPP_OK;
 }
 
@@ -2491,8 +2415,8 @@ sppStatus sppOnpCreate(sppOnPolicyHandle* out, const sppOnPolicyConfig* cfg, int
   hipDeviceProp_t prop;
   SPP_CHECK_HIP(hipGetDeviceProperties(&prop, device));
   o->num_cu = prop.multiProcessorCount;
-  o->nsize[0] = onp_actor_size(cfg->ob, cfg->aout);
-  o->nsize[1] = onp_critic_size(cfg->ob);
+  o->lay[0] = onp_actor_layout(cfg->ob, cfg->aout);
+  o->lay[1] = onp_critic_layout(cfg->ob);
   const int64_t Bp = round_up(cfg->max_batch, 32);
   o->Bpmax = (int)Bp;
   o->pstride = (int)round_up(3 + cfg->aout, 4);
@@ -2529,13 +2453,13 @@ sppStatus sppOnpDestroy(sppOnPolicyHandle o) {
 
 sppStatus sppOnpNetSize(sppOnPolicyHandle o, int net, int64_t* n) {
   SPP_REQUIRE(o && n && (net == 0 || net == 1), SPP_E_INVALID_ARG, "bad net id");
-  *n = o->nsize[net];
+  *n = o->lay[net].size();
   return SPP_OK;
 }
 
 sppStatus sppOnpBindNet(sppOnPolicyHandle o, int net, float* p, float* g, float* m, float* v) {
   SPP_REQUIRE(o && (net == 0 || net == 1) && p && g && m && v, SPP_E_INVALID_ARG, "on-policy bind: bad args");
-  o->net[net] = NetBufs{p, g, m, v, o->nsize[net]};
+  o->net[net] = NetBufs{p, g, m, v, o->lay[net].size()};
   o->pk.release();
   return SPP_OK;
 }
@@ -2944,7 +2868,7 @@ sppStatus sppAllReduceGrads(sppAgentHandle h, int bucket, int world, void* rccl_
   hipStream_t st = S(stream);
   std::vector<std::pair<float*, int64_t>> bufs;
   auto add = [&](int net) {
-    if (h->net[net].g && h->nsize[net] > 0) bufs.push_back({h->net[net].g, h->nsize[net]});
+    if (h->net[net].g && h->lay[net].size() > 0) bufs.push_back({h->net[net].g, h->lay[net].size()});
   };
   const bool all = bucket == SPP_BUCKET_ALL;
   if (all || bucket == SPP_BUCKET_CRITIC) {

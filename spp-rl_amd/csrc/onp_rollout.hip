@@ -16,6 +16,7 @@
 //                     One workgroup per column; plain [rows][ob] arrays.
 #pragma once
 // (included by api.hip after replay.hip and onp.hip: obs_norm1, fkey / funkey, philox, kLogSqrt2PiO)
+#include "layout.h"
 
 namespace spp {
 
@@ -41,7 +42,8 @@ __global__ __launch_bounds__(64) void k_onp_rollout_act(OnpRolloutArgs p) {
   __shared__ float nz[4 * NG];
   const int e = blockIdx.x, lane = threadIdx.x;
   const float* P = p.P;
-  const float *W1 = P + AOUT, *b1 = W1 + 64 * OB, *W2 = b1 + 64, *b2 = W2 + 64 * 64, *W3 = b2 + 64, *b3 = W3 + AOUT * 64;
+  constexpr NetLayout L = onp_actor_layout(OB, AOUT);  // (log_scale = P[0, AOUT))
+  const float *W1 = P + L.w(0), *b1 = P + L.b(0), *W2 = P + L.w(1), *b2 = P + L.b(1), *W3 = P + L.w(2), *b3 = P + L.b(2);
   // every weight this lane needs, in flight before the first use
   float w1[OB], w2[64], w3[AOUT];
 #pragma unroll
