@@ -461,6 +461,17 @@ sppStatus sppOnpCriticApply(sppOnPolicyHandle h, void* stream);
 sppStatus sppOnpActorGrads(sppOnPolicyHandle h, const float* x, const float* act, const float* lp_old,
                            const float* adv, const float* next_obs, int N, float* out4, void* stream);
 sppStatus sppOnpActorApply(sppOnPolicyHandle h, void* stream);
+/* A2C.calculate_advantage (a2c.py:227-265) in one launch: adv = r + gamma (1 - done) V(x_next) - V(x);
+ * q_out (optional) the targets; moments2 (optional) = {mean, std ddof 1} of adv. */
+sppStatus sppOnpTdAdvantage(sppOnPolicyHandle h, const float* x, const float* x_next, const float* rew,
+                            const float* done, int N, float gamma, float* q_out, float* adv_out,
+                            float* moments2, void* stream);
+/* A2C.update_actor (a2c.py:267-286): loss = -mean(logp(act | x) * A), A = adv or (adv - m) / (s + 1e-8) with
+ * moments2 = {m, s}; grads into the actor buffer; out4 = {actor loss, mean logp, dist MSE(dist_act or act,
+ * next_obs) (0 when next_obs is NULL), entropy}.  Apply = sppOnpActorApply. */
+sppStatus sppOnpPgActorGrads(sppOnPolicyHandle h, const float* x, const float* act, const float* adv,
+                             const float* moments2, const float* dist_act, const float* next_obs, int N,
+                             float* out4, void* stream);
 /* PPO_AcM.update_actor_acm / PPO.update_actor minibatch epoch (rltoolkit/acm/on_policy.py:176-207,
  * algorithms/ppo/ppo.py:174-190) in ONE launch: nsteps sequential Adam steps of the Gaussian actor on the
  * clip loss - entropy_coef * entropy over nsteps = ceil(nrows / bs) minibatches: step k's minibatch = rows

@@ -44,6 +44,7 @@
 #endif
 #endif
 #include "onp.hip"
+#include "onp_a2c.hip"
 #include "onp_rollout.hip"
 #include "sgd.hip"
 #include "sgd_mlp.hip"
@@ -2266,11 +2267,19 @@ struct OnpKernels {
   void (*actor)(OnpArgs);
   void (*act)(OnpArgs);
   void (*rollout)(OnpRolloutArgs);
+  void (*td_adv)(OnpA2cArgs);  // (null: no A2C instantiation for these dims)
+  void (*pg_actor)(OnpA2cArgs);
 };
 template <int OB, int AOUT>
 OnpKernels make_onp() {
   using C = OCfg<OB, AOUT>;
-  return {k_onp_value<C>, k_onp_critic_grad<C>, k_onp_actor_grad<C>, k_onp_act<C>, k_onp_rollout_act<OB, AOUT>};
+  OnpKernels k{k_onp_value<C>, k_onp_critic_grad<C>, k_onp_actor_grad<C>, k_onp_act<C>, k_onp_rollout_act<OB, AOUT>,
+               nullptr, nullptr};
+  if constexpr (OB != 3) {  // A2C / A2C_AcM: the HalfCheetah and Hopper pairs
+    k.td_adv = k_onp_td_adv<C>;
+    k.pg_actor = k_onp_pg_actor_grad<C>;
+  }
+  return k;
 }
 static bool find_onp(int ob, int aout, OnpKernels* k) {
   if (ob == 17 && aout == 17) { *k = make_onp<17, 17>(); return true; }  // SPP-PPO HalfCheetah
@@ -2536,6 +2545,50 @@ sppStatus sppOnpActorApply(sppOnPolicyHandle o, void* stream) {
   const double bc1 = 1.0 - std::pow(0.9, (double)o->steps[0]), bc2s = std::sqrt(1.0 - std::pow(0.999, (double)o->steps[0]));
   hipLaunchKernelGGL(k_adam, dim3(std::max(1, std::min(cdiv(o->net[0].n, 1024), 1024)), 1), dim3(256), 0, S(stream),
                      (const AdamJob*)o->d_adam.ptr, (float)(-(o->cfg.actor_lr / bc1)), (float)bc2s, 0.f);
+  SPP_CHECK_HIP(hipGetLastError());
+  return SPP_OK;
+}
+
+sppStatus sppOnpTdAdvantage(sppOnPolicyHandle o, const float* x, const float* x_next, const float* rew,
+                            const float* done, int N, float gamma, float* q_out, float* adv_out, float* moments2,
+                            void* stream) {
+  SPP_REQUIRE(o && x && x_next && rew && done && adv_out, SPP_E_INVALID_ARG, "td advantage: null");
+  SPP_REQUIRE(o->ks.td_adv, SPP_E_SHAPE, "no A2C instantiation for (ob=%d, aout=%d)", o->cfg.ob, o->cfg.aout);
+  hipStream_t st = S(stream);
+  sppStatus s = onp_ready(o, N, st, 1);
+  if (s) return s;
+  OnpA2cArgs a{};
+  a.o = onp_args(o, N);
+  a.o.X = x;
+  a.XN = x_next; a.REW = rew; a.DONE = done; a.gamma = gamma; a.Q_OUT = q_out; a.ADV_OUT = adv_out;
+  hipLaunchKernelGGL(o->ks.td_adv, dim3(onp_grid(o, N)), dim3(256), 0, st, a);
+  SPP_CHECK_HIP(hipGetLastError());
+  if (moments2) {
+    hipLaunchKernelGGL(k_onp_td_moments, dim3(1), dim3(256), 0, st, (const float*)o->part, a.o.Np / 32, o->pstride, N,
+                       moments2);
+    SPP_CHECK_HIP(hipGetLastError());
+  }
+  return SPP_OK;
+}
+
+sppStatus sppOnpPgActorGrads(sppOnPolicyHandle o, const float* x, const float* act, const float* adv,
+                             const float* moments2, const float* dist_act, const float* next_obs, int N, float* out4,
+                             void* stream) {
+  SPP_REQUIRE(o && x && act && adv && out4, SPP_E_INVALID_ARG, "pg actor grads: null");
+  SPP_REQUIRE(o->ks.pg_actor, SPP_E_SHAPE, "no A2C instantiation for (ob=%d, aout=%d)", o->cfg.ob, o->cfg.aout);
+  hipStream_t st = S(stream);
+  sppStatus s = onp_ready(o, N, st, 0);
+  if (s) return s;
+  if (o->dw[1].B != N && (s = onp_dw(o, 1, N))) return s;
+  OnpA2cArgs a{};
+  a.o = onp_args(o, N);
+  a.o.X = x; a.o.ACT = act; a.o.ADV = adv; a.o.NXT = next_obs;
+  a.MOM = moments2; a.DIST_ACT = dist_act;
+  hipLaunchKernelGGL(o->ks.pg_actor, dim3(onp_grid(o, N)), dim3(256), 0, st, a);
+  SPP_CHECK_HIP(hipGetLastError());
+  launch_dw_set(o->dw[1], 0, st);
+  hipLaunchKernelGGL(k_onp_finish_actor, dim3(1), dim3(256), 0, st, (const float*)o->part, a.o.Np / 32, o->pstride, N,
+                     o->cfg.aout, 0.f, (const float*)o->net[0].p, o->net[0].g, out4);
   SPP_CHECK_HIP(hipGetLastError());
   return SPP_OK;
 }

@@ -13,6 +13,8 @@ from .ddpg_acm import DDPG_AcM  # noqa: F401
 from .ddpg import DDPG  # noqa: F401
 from .ppo_acm import PPO_AcM  # noqa: F401
 from .ppo_vanilla import PPO  # noqa: F401
+from .a2c import A2C  # noqa: F401
+from .a2c_acm import A2C_AcM  # noqa: F401
 from .trainer import HostSynthEnv, HostVecEnv, SynthVecEnv  # noqa: F401
 
-__all__ = ["SAC", "SAC_AcM", "DDPG", "DDPG_AcM", "PPO", "PPO_AcM", "SynthVecEnv", "HostVecEnv", "HostSynthEnv", "BufferAcMOffPolicy", "ReplayBuffer", "SppError", "load"]
+__all__ = ["SAC", "SAC_AcM", "DDPG", "DDPG_AcM", "PPO", "PPO_AcM", "A2C", "A2C_AcM", "SynthVecEnv", "HostVecEnv", "HostSynthEnv", "BufferAcMOffPolicy", "ReplayBuffer", "SppError", "load"]

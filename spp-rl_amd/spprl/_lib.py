@@ -131,6 +131,11 @@ _SIGS = {
     "sppOnpActorGrads": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                  c_void_p]),
     "sppOnpActorApply": (c_int, [c_void_p, c_void_p]),
+    # h, x, x_next, rew, done, N, gamma, q_out, adv_out, moments2, stream
+    "sppOnpTdAdvantage": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
+    # h, x, act, adv, moments2, dist_act, next_obs, N, out4, stream
+    "sppOnpPgActorGrads": (c_int, [c_void_p] * 7 + [c_int, c_void_p, c_void_p]),
     "sppOnpAct": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     # h, raw obs, E, mean, std, seed, offset, deterministic, act, logp, norm obs, noise, stream
     "sppOnpRolloutAct": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_uint64, c_uint64, c_int, c_void_p,

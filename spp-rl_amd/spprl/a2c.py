@@ -1,0 +1,108 @@
+"""Vanilla A2C: rltoolkit/algorithms/a2c/a2c.py on the MI355X library -- the class every on-policy algorithm of the
+reference sits on, and the baseline of the SPP-A2C curves.  ``spprl.PPO``'s loop (rollout act, Memory normaliser,
+collect_batch, test, checkpoints: ppo_vanilla.py) with A2C's own update:
+
+  perform_iteration   a2c.py:122-142: collect, update_obs_mean_std, update_critic, calculate_advantage, update_actor
+  calculate_advantage a2c.py:227-265: adv = r + gamma (1 - done) V(s') - V(s), one launch with its moments
+                      (sppOnpTdAdvantage); SPP_A2C_FUSED_ADV=0 runs two sppOnpValue launches and torch arithmetic
+  update_actor        a2c.py:267-286: ONE full-batch Adam step on (-logp * A).mean(), A normalised over the whole
+                      batch with std + 1e-8 (not AdvantageDataset's + 1.2e-7), applied inside sppOnpPgActorGrads
+  loss                {"actor", "critic"} (a2c.py:91)
+
+Ordering quirk kept: the critic and the advantages see observations normalised with the statistics
+updated just before them, but the actor's loss back-propagates through the log-probs stored WHILE ACTING
+(a2c.py:165-166, 279-285), i.e. of observations normalised with the statistics in force during the rollout.  The
+actor has not changed since the rollout, so recomputing those log-probs on the rollout-normalised observations gives
+the same gradient; update(mem) keeps a copy of the statistics before it updates them.
+Out of scope: discrete actions (the reference's CartPole default), data parallelism, TensorBoard.
+"""
+import torch
+
+from . import config
+from ._lib import call, ptr, stream_handle
+from .ppo_vanilla import _ACM_ONLY, PPO
+
+PPO_ONLY = ("epsilon", "ppo_epsilon", "gae_lambda", "kl_div_threshold", "max_ppo_epochs", "ppo_batch_size",
+            "entropy_coef")
+# PPO.__init__'s loop / environment keywords A2C passes through
+_LOOP_KWARGS = ("iterations", "stats_freq", "test_episodes", "return_done", "max_frames", "n_envs", "env", "env_spec",
+                "device", "seed", "loop_seed")
+
+
+def refuse_keywords(owner, kw, acm=True):
+    """TypeError for PPO's keywords (A2C.__init__, a2c.py:17-27, takes none of them) and, for the vanilla class, the
+    AcM's: raised before the library is touched."""
+    bad = sorted(k for k in kw if k in PPO_ONLY)
+    if bad:
+        raise TypeError("%s got unexpected keyword argument(s): %s (PPO options: use PPO%s)"
+                        % (owner, ", ".join(bad), "" if acm else "_AcM"))
+    bad = sorted(k for k in kw if k.startswith("acm_") or k in _ACM_ONLY) if acm else []
+    if bad:
+        raise TypeError("%s got unexpected keyword argument(s): %s (SPP / AcM options: use A2C_AcM)"
+                        % (owner, ", ".join(bad)))
+
+
+def refuse_process_group(owner):
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError("spprl.%s is single-process: data parallelism is PPO_AcM's" % owner)
+
+
+class A2C(PPO):
+    def __init__(self, env_name="HalfCheetah-v2", gamma=config.GAMMA, actor_lr=3e-3, critic_lr=3e-4,
+                 critic_num_target_updates=10, num_critic_updates_per_target=10, normalize_adv=True,
+                 obs_norm_alpha=0.99, batch_size=config.BATCH_SIZE, **kw):
+        refuse_keywords("A2C", kw)
+        config.check_kwargs("A2C", {k: v for k, v in kw.items() if k not in _LOOP_KWARGS},
+                            {k: v for k, v in config.ON_POLICY_NO_EFFECT_KWARGS.items() if k != "obs_norm_alpha"})
+        refuse_process_group("A2C")
+        super().__init__(env_name=env_name, gamma=gamma, actor_lr=actor_lr, critic_lr=critic_lr,
+                         critic_num_target_updates=critic_num_target_updates,
+                         num_critic_updates_per_target=num_critic_updates_per_target, normalize_adv=normalize_adv,
+                         obs_norm_alpha=obs_norm_alpha, batch_size=batch_size, **kw)
+        self.normalize_adv = bool(normalize_adv)
+        self.loss = {"actor": 0.0, "critic": 0.0}  # a2c.py:91
+
+    kl_div_updates_counter = None  # (PPO's counter: A2C has none)
+
+    def pre_train(self):
+        raise AttributeError("vanilla A2C has no ACM pre-training (rltoolkit A2C defines none)")
+
+    def update_acm(self, *a, **k):
+        raise AttributeError("vanilla A2C has no ACM (rltoolkit A2C defines none)")
+
+    update_acm_batches = update_actor_acm = update_acm
+
+    def actor_observations(self, raw_obs, rollout_mean, rollout_std):
+        """The observations the stored log-probs were taken on: standardize_and_clip with the ROLLOUT's statistics
+        (a2c.py:165-166), not the ones update_obs_mean_std has just written."""
+        if rollout_mean is None:
+            return raw_obs
+        out = torch.empty_like(raw_obs)
+        call("sppObsNormalize", ptr(raw_obs), raw_obs.shape[0], self.ob_dim, None, None, ptr(rollout_mean),
+             ptr(rollout_std), 0, 0, ptr(out), stream_handle())
+        self._keep_actor_norm = (raw_obs, rollout_mean, rollout_std)
+        return out
+
+    def update(self, mem):
+        """a2c.py:137-142 on a memory dict (collect_batch's, or a caller's: PPO.update's keys; ``lp`` and ``end``
+        are not read -- the log-probs are recomputed with their graph, the TD advantage needs no episode ends)."""
+        T, E, ob = mem["T"], mem.get("E", self.n_envs), self.ob_dim
+        N = T * E
+        dev = lambda t, dt=torch.float32: torch.as_tensor(t).to(self.device, dt).contiguous()  # noqa: E731
+        mem = dict(mem, obs=dev(mem["obs"]).reshape(N, ob), next_obs=dev(mem["next_obs"]).reshape(N, ob),
+                   start_obs=dev(mem["start_obs"]).reshape(-1, ob))
+        on = self.obs_norm_alpha is not None
+        rollout_mean, rollout_std = (self.obs_mean.clone(), self.obs_std.clone()) if on else (None, None)
+        if on:
+            self.update_obs_mean_std(mem)  # a2c.py:137-138
+        obs, nobs = self.normalize(mem["obs"]), self.normalize(mem["next_obs"])  # Memory.norm_obs / norm_next_obs
+        rew, done = dev(mem["rew"]).reshape(N), dev(mem["done"]).reshape(N)
+        self.nets.update_critic(obs, nobs, rew, done, advantages=False)  # a2c.py:186-222
+        adv, mom = self.nets.td_advantage(obs, nobs, rew, done)  # a2c.py:223, 227-265
+        self.last_advantages = adv
+        out = self.nets.pg_actor_step(self.actor_observations(mem["obs"], rollout_mean, rollout_std),
+                                      dev(mem["act"]).reshape(N, self.ac_dim), adv,
+                                      mom if self.normalize_adv else None)  # a2c.py:267-286
+        self.loss = {"actor": float(out[0].item()), "critic": self.nets.loss["critic"]}

@@ -114,8 +114,9 @@ class OnPolicyNets:
         self._keep = (x, q)
         return loss
 
-    def update_critic(self, obs, next_obs, rew, done):
-        """A2C.update_critic (a2c.py:186-225); returns the advantages of calculate_advantage.  Single-process
+    def update_critic(self, obs, next_obs, rew, done, advantages=True):
+        """A2C.update_critic (a2c.py:186-225); returns the advantages of calculate_advantage (None with
+        advantages=False: the caller takes them from td_advantage).  Single-process
         runs make each target's num_critic_updates_per_target full-batch steps in one persistent launch
         (sppOnpCriticSteps); data-parallel ranks all-reduce every step's gradient (critic_step)."""
         obs, next_obs, rew, done = (self._dev(t) for t in (obs, next_obs, rew, done))
@@ -136,11 +137,55 @@ class OnPolicyNets:
         self.loss["critic"] = float(total.item()) / (self.critic_num_target_updates *
                                                      self.num_critic_updates_per_target)
         self._sync_check()
+        if not advantages:
+            return None
         with torch.no_grad():
             q = rew + self.gamma * (1 - done) * self.value(next_obs)
             return q - self.value(obs)
 
+    def td_advantage(self, obs, next_obs, rew, done, want_q=False):
+        """A2C.calculate_advantage (a2c.py:227-265): (advantages [N], moments {mean, std ddof 1} [2]) -- with
+        want_q also the targets q.  One launch (sppOnpTdAdvantage); SPP_A2C_FUSED_ADV=0 runs the unfused sequence
+        instead: two sppOnpValue launches, torch arithmetic, the moments by torch."""
+        import os
+
+        obs, next_obs, rew, done = (self._dev(t) for t in (obs, next_obs, rew, done))
+        rew, done = rew.reshape(-1), done.reshape(-1)
+        N = obs.shape[0]
+        if os.environ.get("SPP_A2C_FUSED_ADV", "1") == "0":
+            q = rew + self.gamma * (1 - done) * self.value(next_obs)
+            adv = q - self.value(obs)
+            mom = torch.stack([adv.mean(), adv.std()])
+        else:
+            adv, mom = torch.empty(N, device=self.device), torch.empty(2, device=self.device)
+            q = torch.empty(N, device=self.device) if want_q else None
+            call("sppOnpTdAdvantage", self._h, ptr(obs), ptr(next_obs), ptr(rew), ptr(done), N, float(self.gamma),
+                 ptr(q), ptr(adv), ptr(mom), stream_handle())
+            self._keep = (obs, next_obs, rew, done)
+        return (adv, mom, q) if want_q else (adv, mom)
+
     # ------------------------------------------------------------------ actor
+    def pg_actor_step(self, x, act, adv, moments, dist_act=None, next_obs=None, out=None, grad_sum=None):
+        """A2C.update_actor (a2c.py:267-286): one full-batch Adam step on -mean(logp(act | x) * A), A = adv or --
+        moments = {mean, std} given -- (adv - mean) / (std + 1e-8).  out4 = {actor loss, mean logp, dist MSE(dist_act
+        or act, next_obs), entropy}.  grad_sum (a device buffer the caller keeps) is update_actor_acm's gradient
+        that is never zeroed (on_policy.py:117-124): the step's gradient is added to it and the sum is applied."""
+        if self.allreduce is not None:
+            raise NotImplementedError("pg_actor_step is single-process")
+        x, act, adv = self._dev(x), self._dev(act), self._dev(adv).reshape(-1)
+        da = self._dev(dist_act) if dist_act is not None else None
+        nxt = self._dev(next_obs) if next_obs is not None else None
+        if out is None:
+            out = torch.empty(4, device=self.device)
+        call("sppOnpPgActorGrads", self._h, ptr(x), ptr(act), ptr(adv), ptr(moments), ptr(da), ptr(nxt), x.shape[0],
+             ptr(out), stream_handle())
+        if grad_sum is not None:
+            grad_sum.add_(self.grads[0])
+            self.grads[0].copy_(grad_sum)
+        call("sppOnpActorApply", self._h, stream_handle())
+        self._keep = (x, act, adv, moments, da, nxt)
+        return out
+
     def actor_step(self, x, act, lp_old, adv, next_obs=None, out=None):
         """One minibatch step; ``out`` (4 floats: actor loss, KL, dist, entropy) is written, not
         accumulated, so a caller may hand in rows of a preallocated [steps][4] buffer."""

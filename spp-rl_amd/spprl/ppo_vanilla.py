@@ -22,7 +22,8 @@ for up to onpolicy.FUSED_ACT_MAX_ROWS envs; SPP_PPO_FUSED_ACT=0 or more envs run
 sppOnpAct on the same draws.  The actor's minibatch steps run one by one (sppOnpActorGrads / Apply) unless
 SPP_PPO_EPOCH_KERNEL=1 selects the one-launch epochs (sppOnpActorEpoch at (17, 6) / (11, 3)): measured, they did not
 raise env-steps/s by more than the run-to-run spread at the reference cadence.
-Out of scope: A2C's own actor loss, discrete actions, data parallelism, TensorBoard.
+A2C's own update (TD advantage, one policy-gradient step) is spprl.A2C (a2c.py), a subclass of this loop.
+Out of scope: discrete actions, data parallelism, TensorBoard.
 """
 import numpy as np
 import torch
