@@ -362,6 +362,9 @@ sppStatus sppReplaySetAcmColumns(sppReplayHandle h, const int* cols_host, int n)
  * GetTiming synchronises on the recorded events, returns total ms and launch
  * counts per kind, and clears them. */
 sppStatus sppAgentSetTiming(sppAgentHandle h, int enable);
+/* Which cuts of the SAC phases' stage split this handle runs (bit 0: the actor backward's per-sample stages as
+ * their own kernel); 0 for handles whose shapes have none, or under SPP_STAGE_SPLIT=0 (read at creation). */
+sppStatus sppAgentStageSplit(sppAgentHandle h, int* bits_out);
 sppStatus sppAgentGetTiming(sppAgentHandle h, double* ms_out /*[5]*/, int64_t* count_out /*[5]*/);
 
 /* Rollout action (rltoolkit/acm/off_policy/ddpg_acm.py:40-50 noise_action +

@@ -934,6 +934,12 @@ struct sppAgent {
   uint64_t* MASK = nullptr;   // and the trunk's ReLU masks [tile][4][64]
   // min-critic split of the one-wave actor phase (sac.hip: AcmScratch; SPP_MINQ_SPLIT=0: the one-kernel phase, A/B)
   bool minq_split = false;
+  // stage split of the phase kernels (sac.hip), one bit per cut; SPP_STAGE_SPLIT=0: today's kernels (A/B).
+  //   bit 0  k_sac_actor_heads<C, true> -> k_sac_heads_stage, k_sac_actor_trunk_bwd
+  //   bit 1  k_sac_actor_phase<C, true> -> k_sac_trunk_fwd<C, true>, k_sac_squash_stage<C, true>, the critics
+  //   bit 2  k_sac_critic_phase         -> k_sac_trunk_fwd<C, false>, k_sac_squash_stage<C, false>, the rest
+  int stage_split = 0;
+  float *THD = nullptr, *SCA = nullptr, *SLP = nullptr;  // its hand-overs (SacArgs)
   AcmScratch mq{};  // its hand-over buffers (SEL ... DCA)
   // ACM regression scratch
   float *RX = nullptr, *RZ1 = nullptr, *RZ2 = nullptr, *RP1 = nullptr, *RP2 = nullptr, *RP3 = nullptr;
@@ -1361,6 +1367,14 @@ static void launch_adam(sppAgent* a, int first, int count, int64_t n, int64_t st
                      (const AdamJob*)(a->d_adam.ptr + first), (float)(-(lr / bc1)), (float)bc2s, tau);
 }
 
+// Workgroups per CU of the stage kernels' grids (their LDS use lets three share a CU)
+constexpr int kStageWGPerCU = 3;
+constexpr int kStageSplitAll = 7;
+constexpr int kStageSplitDefault = kStageSplitAll;
+static int stage_grid(sppAgent* a, int Bp) {
+  return std::max(1, std::min(cdiv(Bp / 32, kWavesPerWG), kStageWGPerCU * a->num_cu));
+}
+
 static SacArgs make_args(sppAgent* a, int B) {
   SacArgs p{};
   p.B = B;
@@ -1389,6 +1403,7 @@ static SacArgs make_args(sppAgent* a, int B) {
   p.actor_targ = a->actor_targ;
   p.AH1 = a->AH1; p.AH2 = a->AH2; p.AD1 = a->AD1; p.AD2 = a->AD2; p.ADH = a->ADH;
   p.part = a->part;
+  p.THD = a->THD; p.SCA = a->SCA; p.SLP = a->SLP;
   p.nseg = (int)a->tab.size();
   for (int i = 0; i < p.nseg; ++i) p.seg[i] = a->tab[i];
   // limits and normaliser vectors (read per output slot by the squash / head epilogues: LDS
@@ -1405,6 +1420,30 @@ static SacArgs make_args(sppAgent* a, int B) {
   p.t_alim = X(a->limits.ptr + aout, a->cfg.ac);
   p.t_n0 = X(p.min_max ? a->lo : a->mean, aout);
   p.t_n1 = X(p.min_max ? a->hi : a->std, aout);
+  return p;
+}
+
+// The stage kernels' argument block: their LDS table holds only the segments they read, packed from offset 0:
+// the ACM's three bias vectors and the limit / normaliser vectors (the other networks' bias / fc3 offsets of
+// the block are not read by them).
+static SacArgs stage_args(const sppAgent* a, const SacArgs& full) {
+  SacArgs p = full;
+  const int n0 = (int)a->tab.size();
+  p.nseg = 0;
+  int off = 0;
+  auto keep = [&](int i) {
+    TabSeg g = full.seg[i];
+    g.off = off;
+    p.seg[p.nseg++] = g;
+    off += g.npad;
+    return g.off;
+  };
+  for (int i = 0; i < n0; ++i) {
+    if (full.seg[i].off == full.acm.tb1) p.acm.tb1 = keep(i);
+    else if (full.seg[i].off == full.acm.tb2) p.acm.tb2 = keep(i);
+    else if (full.seg[i].off == full.acm.tb3) p.acm.tb3 = keep(i);
+  }
+  p.t_lim = keep(n0); p.t_alim = keep(n0 + 1); p.t_n0 = keep(n0 + 2); p.t_n1 = keep(n0 + 3);
   return p;
 }
 
@@ -1452,6 +1491,12 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
     a->team_ok = !(t && t[0] == '0');
     const char* m = getenv("SPP_MINQ_SPLIT");
     a->minq_split = ks.actor_fwd && ks.actor_minq && ks.actor_bwd && !(m && m[0] == '0');
+    const char* g = getenv("SPP_STAGE_SPLIT");
+    const int want = g ? atoi(g) : kStageSplitDefault;
+    const bool tab_fits = 128 + 3 * round_up(std::max(cfg->aout, 1), 32) + round_up(std::max(cfg->ac, 1), 32) <= kStageTab;
+    const bool have = ks.heads_stage && ks.trunk_bwd && ks.trunk_fwd_a && ks.squash_a && ks.critics_a &&
+                      ks.trunk_fwd_c && ks.squash_c && ks.critic_rest;
+    if (a->minq_split && have && tab_fits) a->stage_split = want & kStageSplitAll;
   }
   const int ob = cfg->ob, aout = cfg->aout, ac = cfg->ac;
   a->cin = ob + (cfg->acm_critic ? ac : aout);
@@ -1495,6 +1540,9 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
   const int64_t ca = a->cin - ob;
   const int64_t oSEL = mq ? take(1) : 0, oCM = mq ? take(32) : 0, oCNT = mq ? take(1) : 0, oLIST = mq ? take(2) : 0,
                 oDCA = mq ? take(2 * ca) : 0;
+  // stage split hand-overs: target heads, the critics' action input, log pi
+  const bool ss = a->stage_split != 0;
+  const int64_t oTHD = ss ? take(2 * aout) : 0, oSCA = ss ? take(ca) : 0, oSLP = ss ? take(1) : 0;
   const int64_t oPart = total;
   total += ntiles * kBParts + 64;
   const int64_t oAux = total;
@@ -1527,6 +1575,9 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
     q.LIST[1] = q.LIST[0] + Bp;
     q.DCA[0] = b + oDCA;
     q.DCA[1] = q.DCA[0] + ca * Bp;
+  }
+  if (ss) {
+    a->THD = b + oTHD; a->SCA = b + oSCA; a->SLP = b + oSLP;
   }
   a->RX = b + oRX; a->RZ1 = b + oRZ1; a->RZ2 = b + oRZ2; a->RP1 = b + oRP1; a->RP2 = b + oRP2; a->RP3 = b + oRP3;
   if (dd) {
@@ -1647,7 +1698,14 @@ static sppStatus critic_grads_staged(sppAgentHandle a, float* losses, hipStream_
   const int grid = sac_critic_grid(a, p.Bp);
   tmark(a, 0, st);
   const bool team = phase_team(a, p.Bp);
-  hipLaunchKernelGGL(team ? a->ks.critic_team : a->ks.critic, dim3(grid), dim3(team ? 64 * kTeamCritic : 256), 0, st, p);
+  if (!team && (a->stage_split & 4)) {
+    // stage split: the target actor's trunk; the squash and the ACM forward; both target critics and the critics
+    hipLaunchKernelGGL(a->ks.trunk_fwd_c, dim3(tile_grid(a, p.Bp)), dim3(256), 0, st, p, a->mq);
+    hipLaunchKernelGGL(a->ks.squash_c, dim3(stage_grid(a, p.Bp)), dim3(256), 0, st, stage_args(a, p), a->mq);
+    hipLaunchKernelGGL(a->ks.critic_rest, dim3(grid), dim3(256), 0, st, p);
+  } else {
+    hipLaunchKernelGGL(team ? a->ks.critic_team : a->ks.critic, dim3(grid), dim3(team ? 64 * kTeamCritic : 256), 0, st, p);
+  }
   tmark(a, 0, st);
   SPP_CHECK_HIP(hipGetLastError());
   tmark(a, 2, st);
@@ -1698,12 +1756,23 @@ static sppStatus actor_grads(sppAgentHandle a, float* losses, hipStream_t st) {
     // min-critic split: forward to q = min(Q1, Q2); the two lists of samples by chosen critic; that critic's
     // backward over the regrouped samples; everything behind it in the original order (sac.hip)
     z = a->mq;
-    hipLaunchKernelGGL(a->ks.actor_fwd, dim3(grid), dim3(256), 0, st, p, z);
+    if (a->stage_split & 2) {
+      hipLaunchKernelGGL(a->ks.trunk_fwd_a, dim3(grid), dim3(256), 0, st, p, z);
+      hipLaunchKernelGGL(a->ks.squash_a, dim3(stage_grid(a, p.Bp)), dim3(256), 0, st, stage_args(a, p), z);
+      hipLaunchKernelGGL(a->ks.critics_a, dim3(grid), dim3(256), 0, st, p, z);
+    } else {
+      hipLaunchKernelGGL(a->ks.actor_fwd, dim3(grid), dim3(256), 0, st, p, z);
+    }
     hipLaunchKernelGGL(k_minq_scan, dim3(1), dim3(kMinqScanThreads), 0, st, (const uint32_t*)z.CNT, z.OFF, z.NG, p.Bp / 32);
     hipLaunchKernelGGL(k_minq_scatter, dim3(cdiv(p.Bp, 256)), dim3(256), 0, st, (const uint8_t*)z.SEL,
                        (const uint32_t*)z.OFF, z.LIST[0], z.LIST[1], p.Bp);
     hipLaunchKernelGGL(a->ks.actor_minq, dim3(grid), dim3(256), 0, st, p, z);
-    hipLaunchKernelGGL(a->ks.actor_bwd, dim3(grid), dim3(256), 0, st, p, z);
+    if (a->stage_split & 1) {
+      hipLaunchKernelGGL(a->ks.heads_stage, dim3(stage_grid(a, p.Bp)), dim3(256), 0, st, stage_args(a, p), z);
+      hipLaunchKernelGGL(a->ks.trunk_bwd, dim3(grid), dim3(256), 0, st, p, z);
+    } else {
+      hipLaunchKernelGGL(a->ks.actor_bwd, dim3(grid), dim3(256), 0, st, p, z);
+    }
   } else {
     hipLaunchKernelGGL(team ? a->ks.actor_team : a->ks.actor, dim3(grid), dim3(team ? 64 * kTeamActor : 256), 0, st, p, z);
     if (a->ks.actor_heads) hipLaunchKernelGGL(a->ks.actor_heads, dim3(grid), dim3(256), 0, st, p, z);
@@ -1729,6 +1798,12 @@ sppStatus sppSacAcmActorGrads(sppAgentHandle a, const float* eps_cur, float* los
     hipLaunchKernelGGL(k_eps_copy_fm, dim3(cdiv((int64_t)a->cfg.aout * Bp, 256)), dim3(256), 0, S(stream), eps_cur,
                        a->EPS2, a->cfg.aout, B, Bp);
   return actor_grads(a, losses, S(stream));
+}
+
+sppStatus sppAgentStageSplit(sppAgentHandle a, int* bits_out) {
+  SPP_REQUIRE(a && bits_out, SPP_E_INVALID_ARG, "null");
+  *bits_out = a->stage_split;
+  return SPP_OK;
 }
 
 sppStatus sppAgentBindAlphaGrad(sppAgentHandle a, float* g) {

@@ -35,6 +35,17 @@ struct KernelSet {
   void (*actor_fwd)(SacArgs, AcmScratch);
   void (*actor_minq)(SacArgs, AcmScratch);
   void (*actor_bwd)(SacArgs, AcmScratch);
+  // stage split of actor_bwd (narrow heads; sac.hip): the per-sample stages as a high-occupancy kernel, then the
+  // trunk backward; null where there is none
+  void (*heads_stage)(SacArgs, AcmScratch);
+  void (*trunk_bwd)(SacArgs, AcmScratch);
+  // stage split of actor_fwd and of the critic phase: trunk, squash + ACM forward, the rest
+  void (*trunk_fwd_a)(SacArgs, AcmScratch);
+  void (*squash_a)(SacArgs, AcmScratch);
+  void (*critics_a)(SacArgs, AcmScratch);
+  void (*trunk_fwd_c)(SacArgs, AcmScratch);
+  void (*squash_c)(SacArgs, AcmScratch);
+  void (*critic_rest)(SacArgs);
 };
 
 template <int OB, int AOUT, int AC, bool ACMC, bool BF = false>
@@ -52,6 +63,16 @@ KernelSet make_kset() {
     ks.actor_fwd = k_sac_actor_phase<C, true>;
     ks.actor_minq = k_sac_minq_backward<C>;
     ks.actor_bwd = k_sac_actor_heads<C, true>;
+    if constexpr (C::NB_PAIR <= 2) {
+      ks.heads_stage = k_sac_heads_stage<C>;
+      ks.trunk_bwd = k_sac_actor_trunk_bwd<C>;
+      ks.trunk_fwd_a = k_sac_trunk_fwd<C, true>;
+      ks.squash_a = k_sac_squash_stage<C, true>;
+      ks.critics_a = k_sac_actor_phase<C, true, true>;
+      ks.trunk_fwd_c = k_sac_trunk_fwd<C, false>;
+      ks.squash_c = k_sac_squash_stage<C, false>;
+      ks.critic_rest = k_sac_critic_phase<C, true>;
+    }
   }
   return ks;
 }

@@ -188,6 +188,26 @@ __device__ __forceinline__ void load_pair(f32x16 (&t)[C::NB_PAIR], const float* 
     }
 }
 
+// The same tile from a feature-major global array HD [2*AOUT][ld] (rows mu | logsig) at the lane's pairing
+// offset vp; slots j >= AOUT hold 0, as load_pair's do (the bounded resource alone would not give that: slot j
+// of the mu rows lands in the logsig rows).
+template <class C>
+__device__ __forceinline__ void load_pair_gl(f32x16 (&t)[C::NB_PAIR], const float* HD, int ld4, uint32_t vp) {
+  const rsrc_t hr = rsrc_n(HD, 2 * C::AOUT * ld4);
+  const int h8 = 8 * (lane_id() >> 5);
+#pragma unroll
+  for (int ib = 0; ib < C::NB_PAIR; ++ib)
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int j0 = 16 * ib + r;
+      const bool ok = j0 + h8 < C::AOUT;
+      const float mu = fm_ldb(hr, j0, ld4, vp);
+      const float ls = fm_ldb(hr, C::AOUT + j0, ld4, vp);
+      t[ib][r] = ok ? mu : 0.f;
+      t[ib][r + 8] = ok ? ls : 0.f;
+    }
+}
+
 // Concatenated input tile: blocks [0, NB0) natural from global X (F0 units),
 // blocks [NB0, NB0+NB1) natural from the LDS image rows [0, F1).
 template <int NB0, int NB1>
@@ -336,10 +356,12 @@ struct Fc1Gen {
 // Actor trunk: x -> relu(L1) -> relu(L2) -> heads into LDS rows [0, NHR): SAC
 // (mu | logsig), NHR = 2*AOUT; DDPG fc3 pre-activation, NHR = AOUT (NBH blocks).
 // ST: store h1 / h2 feature-major (H1g, H2g).  Returns the ReLU masks.
-template <class C, bool ST, int NBH = C::NB_H2, int NHR = 2 * C::AOUT>
+// HG: the heads go feature-major to HDg [NHR][ld] at the sample's own column instead of into the image.
+template <class C, bool ST, int NBH = C::NB_H2, int NHR = 2 * C::AOUT, bool HG = false>
 __device__ __forceinline__ void actor_trunk(const ActorDev& A, const float* X, int xbytes, const Lane& L, float* H1g,
                                             float* H2g,
-                                            uint64_t& m1lo, uint64_t& m1hi, uint64_t& m2lo, uint64_t& m2hi) {
+                                            uint64_t& m1lo, uint64_t& m1hi, uint64_t& m2lo, uint64_t& m2hi,
+                                            float* HDg = nullptr) {
   {
     f32x16 x[C::NB_OB];
     gm_load<C::NB_OB>(x, X, xbytes, C::OB, L.ld4, L.vo);
@@ -379,7 +401,10 @@ __device__ __forceinline__ void actor_trunk(const ActorDev& A, const float* X, i
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int ur = 32 * ob + ru(q);
-        if (ur + L.h4 < NHR) L.bl[ur * 32] = acc[q];
+        if (ur + L.h4 < NHR) {
+          if constexpr (HG) fm_st(rsrc(HDg), ur, L.ld4, L.vo, acc[q]);
+          else L.bl[ur * 32] = acc[q];
+        }
       }
     });
   }
@@ -548,7 +573,9 @@ __device__ __forceinline__ float squash_write(const SacArgs& p, const f32x16 (&h
 }
 
 // ============================================================================ critic phase
-template <class C>
+// STAGED (the stage split): the target action comes from k_sac_trunk_fwd / k_sac_squash_stage; the kernel starts
+// at the target critics, from their action input (p.SCA) and log pi' (p.SLP).
+template <class C, bool STAGED = false>
 __global__ __launch_bounds__(256, 1) void k_sac_critic_phase(SacArgs p) {
   __shared__ __attribute__((aligned(16))) float smem[kWavesPerWG * kLdsPerWave];
   __shared__ __attribute__((aligned(16))) float tbl[kTabMax];
@@ -567,25 +594,31 @@ __global__ __launch_bounds__(256, 1) void k_sac_critic_phase(SacArgs p) {
     const int b = L.b;
     const bool valid = b < p.B;
     uint64_t d0 = 0, d1 = 0, d2 = 0, d3 = 0;
-    // ---- target action: a' ~ pi(s'), a'_d, logpi'   (sac_acm.py:44-45)
-    SPP_TP(0);
-    actor_trunk<C, false>(p.actor, p.S2, C::OB * L.ld4, L, nullptr, nullptr, d0, d1, d2, d3);
     float lp2;
-    {
-      f32x16 hd[C::NB_PAIR];
-      load_pair<C>(hd, big);
-      lp2 = squash_write<C, true>(p, hd, p.EPS1, L);
-    }
-    SPP_TP(4);
-    // ---- critic-target input: [s' | ACM(s', a'_d)] or [s' | a'_d]   (:46-48)
     f32x16 tin[C::NB_CIN];
-    if constexpr (C::ACMC) {
-      f32x16 xin[C::NB_ACMIN];
-      load_cat_gl<C::NB_OB, C::NB_AOUT>(xin, p.S2, C::OB * L.ld4, C::OB, L.ld4, L.vo, big, C::AOUT);
-      acm_forward<C, false>(p, xin, L, nullptr, nullptr, nullptr);
-      load_cat_gl<C::NB_OB, C::NB_CA>(tin, p.S2, C::OB * L.ld4, C::OB, L.ld4, L.vo, small, C::AC);
+    if constexpr (STAGED) {
+      SPP_TP(0);
+      load_cat_gg<C::NB_OB, C::NB_CA>(tin, p.S2, C::OB, p.SCA, C::CA, L.ld4, L.vo);
+      lp2 = p.SLP[b];
     } else {
-      load_cat_gl<C::NB_OB, C::NB_CA>(tin, p.S2, C::OB * L.ld4, C::OB, L.ld4, L.vo, big, C::AOUT);
+      // ---- target action: a' ~ pi(s'), a'_d, logpi'   (sac_acm.py:44-45)
+      SPP_TP(0);
+      actor_trunk<C, false>(p.actor, p.S2, C::OB * L.ld4, L, nullptr, nullptr, d0, d1, d2, d3);
+      {
+        f32x16 hd[C::NB_PAIR];
+        load_pair<C>(hd, big);
+        lp2 = squash_write<C, true>(p, hd, p.EPS1, L);
+      }
+      SPP_TP(4);
+      // ---- critic-target input: [s' | ACM(s', a'_d)] or [s' | a'_d]   (:46-48)
+      if constexpr (C::ACMC) {
+        f32x16 xin[C::NB_ACMIN];
+        load_cat_gl<C::NB_OB, C::NB_AOUT>(xin, p.S2, C::OB * L.ld4, C::OB, L.ld4, L.vo, big, C::AOUT);
+        acm_forward<C, false>(p, xin, L, nullptr, nullptr, nullptr);
+        load_cat_gl<C::NB_OB, C::NB_CA>(tin, p.S2, C::OB * L.ld4, C::OB, L.ld4, L.vo, small, C::AC);
+      } else {
+        load_cat_gl<C::NB_OB, C::NB_CA>(tin, p.S2, C::OB * L.ld4, C::OB, L.ld4, L.vo, big, C::AOUT);
+      }
     }
     // ---- soft-min twin target (:50-56)
     SPP_TP(5);
@@ -884,11 +917,58 @@ __device__ __forceinline__ float heads_backward(const SacArgs& p, const Lane& L,
   return dist_part;
 }
 
+// The chosen critics' action-input gradients of the min-critic split, read back at the sample's own column:
+// dca = 0; dca += critic 1's; dca += critic 2's, as the one-kernel phase sums them: there the critic
+// that lost the min adds the exact +0 its zero delta2 gives.  Rows >= CA are not read by anything.
+template <class C>
+__device__ __forceinline__ void load_dca(const AcmScratch& z, const Lane& L, f32x16 (&dca)[C::NB_CA]) {
+  const int sel = z.SEL[L.b];
+  const rsrc_t r1 = rsrc_n(z.DCA[0], C::CA * L.ld4), r2 = rsrc_n(z.DCA[1], C::CA * L.ld4);
+#pragma unroll
+  for (int ib = 0; ib < C::NB_CA; ++ib)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int ur = 32 * ib + ru(q);
+      float v1 = 0.f, v2 = 0.f;
+      if (ur < C::CA) {  // (rows ur + 4h >= CA of the upper lane half read 0 through the bounded resource)
+        v1 = fm_ldb(r1, ur, L.ld4, L.vo);
+        v2 = fm_ldb(r2, ur, L.ld4, L.vo);
+      }
+      v1 = (sel & 1) ? v1 : 0.f;
+      v2 = (sel & 2) ? v2 : 0.f;
+      dca[ib][q] = fadd_rn(fadd_rn(0.f, v1), v2);
+    }
+}
+
+// Actor trunk backward from d loss / d heads in the pairing layout: dh2 = Wh^T dheads * relu'(h2),
+// dh1 = W2^T dh2 * relu'(h1), both stored feature-major (AD2 / AD1, the weight-gradient operands).
+template <class C>
+__device__ __forceinline__ void actor_trunk_backward(const SacArgs& p, const Lane& L, const f32x16 (&hd)[C::NB_PAIR],
+                                                     uint64_t a1lo, uint64_t a1hi, uint64_t a2lo, uint64_t a2hi) {
+  dense<C::NB_PAIR, C::RV_PAIR, C::BF>(p.actor.WhT, 8, hd, nullptr, [&](int ob, const f32x16& acc) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int ur = 32 * ob + ru(q);
+      const float v = getbit(a2lo, a2hi, ob, q) ? acc[q] : 0.f;
+      L.bl[ur * 32] = v;
+      op_st<C::BF>(rsrc(p.AD2), ur, L.ld4, L.vo, v);
+    }
+  });
+  dense_lds<8, C::BF>(p.actor.W2T, L.img, nullptr, [&](int ob, const f32x16& acc) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+      op_st<C::BF>(rsrc(p.AD1), 32 * ob + ru(q), L.ld4, L.vo, getbit(a1lo, a1hi, ob, q) ? acc[q] : 0.f);
+  });
+}
+
 // SPLIT (the min-critic split, fp32 sets): the kernel ends after q = min(Q1, Q2) and hands the rest of the
 // phase to k_sac_minq_backward (the chosen critic's backward, samples regrouped by critic) and
 // k_sac_actor_heads<C, true> (everything after it, in the original sample order).
-template <class C, bool SPLIT = false>
+// STAGED (the stage split, with SPLIT): a, logpi and the critics' input come from k_sac_trunk_fwd /
+// k_sac_squash_stage (p.SCA, p.SLP; the trunk kernel has stored the trunk's masks); the kernel is the critics.
+template <class C, bool SPLIT = false, bool STAGED = false>
 __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratch z) {
+  static_assert(SPLIT || !STAGED, "the stage split cuts the split phase");
   __shared__ float smem[kWavesPerWG * kLdsPerWave];
   __shared__ __attribute__((aligned(16))) float tbl[kTabMax];
   SPP_TP_INIT();
@@ -906,39 +986,46 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
     const float g_lp = valid ? alpha * p.inv_B : 0.f;  // d loss / d logpi_b
     // ---- a, logpi = actor(s)  (sac_acm.py:137)
     uint64_t a1lo = 0, a1hi = 0, a2lo = 0, a2hi = 0;
-    SPP_TP(26);
-    actor_trunk<C, true>(p.actor, p.S, C::OB * L.ld4, L, p.AH1, p.AH2, a1lo, a1hi, a2lo, a2hi);
-    SPP_TP(27);  // actor trunk
     f32x16 hd[C::NB_PAIR];
-    load_pair<C>(hd, big);
-    const float lp = squash_write<C>(p, hd, p.EPS2, L);  // a_d -> big rows [0, AOUT)
-    SPP_TP(28);  // squash
-    // Wide heads (Ant): park mu / raw log-std in the ADH rows the heads backward overwrites
-    // (same lane, same element), instead of keeping NB_PAIR tiles live through the critics.
-    // The split forward kernel parks them for k_sac_actor_heads whatever their width.
-    constexpr bool kWide = C::NB_PAIR > 2;
-    constexpr bool kParkHeads = kWide || SPLIT;
-    if constexpr (kParkHeads) {
-#pragma unroll
-      for (int ib = 0; ib < C::NB_PAIR; ++ib)
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          const int j0 = 16 * ib + r;
-          if (j0 + 8 * L.h < C::AOUT) {
-            fm_st(rsrc(p.ADH), j0, L.ld4, L.vp, hd[ib][r]);
-            fm_st(rsrc(p.ADH), C::AOUT + j0, L.ld4, L.vp, hd[ib][r + 8]);
-          }
-        }
-    }
-    // ---- critic input [s | ACM(s, a_d)] or [s | a_d]  (:67-72)
+    float lp;
     f32x16 cin[C::NB_CIN];
-    if constexpr (C::ACMC) {
-      f32x16 xin[C::NB_ACMIN];
-      load_cat_gl<C::NB_OB, C::NB_AOUT>(xin, p.S, C::OB * L.ld4, C::OB, L.ld4, L.vo, big, C::AOUT);
-      acm_forward<C, true>(p, xin, L, z.Z1, z.Z2, z.T3);
-      load_cat_gl<C::NB_OB, C::NB_CA>(cin, p.S, C::OB * L.ld4, C::OB, L.ld4, L.vo, small, C::AC);
+    constexpr bool kWide = C::NB_PAIR > 2;
+    if constexpr (STAGED) {
+      SPP_TP(26);
+      load_cat_gg<C::NB_OB, C::NB_CA>(cin, p.S, C::OB, p.SCA, C::CA, L.ld4, L.vo);
+      lp = p.SLP[b];
     } else {
-      load_cat_gl<C::NB_OB, C::NB_CA>(cin, p.S, C::OB * L.ld4, C::OB, L.ld4, L.vo, big, C::AOUT);
+      SPP_TP(26);
+      actor_trunk<C, true>(p.actor, p.S, C::OB * L.ld4, L, p.AH1, p.AH2, a1lo, a1hi, a2lo, a2hi);
+      SPP_TP(27);  // actor trunk
+      load_pair<C>(hd, big);
+      lp = squash_write<C>(p, hd, p.EPS2, L);  // a_d -> big rows [0, AOUT)
+      SPP_TP(28);  // squash
+      // Wide heads (Ant): park mu / raw log-std in the ADH rows the heads backward overwrites
+      // (same lane, same element), instead of keeping NB_PAIR tiles live through the critics.
+      // The split forward kernel parks them for k_sac_actor_heads whatever their width.
+      constexpr bool kParkHeads = kWide || SPLIT;
+      if constexpr (kParkHeads) {
+#pragma unroll
+        for (int ib = 0; ib < C::NB_PAIR; ++ib)
+#pragma unroll
+          for (int r = 0; r < 8; ++r) {
+            const int j0 = 16 * ib + r;
+            if (j0 + 8 * L.h < C::AOUT) {
+              fm_st(rsrc(p.ADH), j0, L.ld4, L.vp, hd[ib][r]);
+              fm_st(rsrc(p.ADH), C::AOUT + j0, L.ld4, L.vp, hd[ib][r + 8]);
+            }
+          }
+      }
+      // ---- critic input [s | ACM(s, a_d)] or [s | a_d]  (:67-72)
+      if constexpr (C::ACMC) {
+        f32x16 xin[C::NB_ACMIN];
+        load_cat_gl<C::NB_OB, C::NB_AOUT>(xin, p.S, C::OB * L.ld4, C::OB, L.ld4, L.vo, big, C::AOUT);
+        acm_forward<C, true>(p, xin, L, z.Z1, z.Z2, z.T3);
+        load_cat_gl<C::NB_OB, C::NB_CA>(cin, p.S, C::OB * L.ld4, C::OB, L.ld4, L.vo, small, C::AC);
+      } else {
+        load_cat_gl<C::NB_OB, C::NB_CA>(cin, p.S, C::OB * L.ld4, C::OB, L.ld4, L.vo, big, C::AOUT);
+      }
     }
     SPP_TP(29);  // ACM forward
     // ---- q = min(Q1, Q2)(s, c)  (:73-75), masks kept for the backward
@@ -963,11 +1050,13 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
       cm1[0] = make_uint4((uint32_t)mb0, (uint32_t)(mb0 >> 32), (uint32_t)mb1, (uint32_t)(mb1 >> 32));
       cm1[1] = make_uint4((uint32_t)mb2, (uint32_t)(mb2 >> 32), (uint32_t)mb3, (uint32_t)(mb3 >> 32));
       const int n1 = __popcll(__ballot(L.h == 0 && (sel & 1))), n2 = __popcll(__ballot(L.h == 0 && (sel & 2)));
-      uint64_t* mk = z.MASK + (int64_t)tile * 4 * 64 + lane;
-      mk[0] = a1lo;
-      mk[64] = a1hi;
-      mk[128] = a2lo;
-      mk[192] = a2hi;
+      if constexpr (!STAGED) {
+        uint64_t* mk = z.MASK + (int64_t)tile * 4 * 64 + lane;
+        mk[0] = a1lo;
+        mk[64] = a1hi;
+        mk[128] = a2lo;
+        mk[192] = a2hi;
+      }
       const float ps = wave_sum((valid && L.h == 0) ? fsub_rn(alpha * lp, qmin) : 0.f);
       const float pl = wave_sum((valid && L.h == 0) ? lp : 0.f);
       if (lane == 0) {
@@ -1050,22 +1139,7 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
     const float dist_part = heads_backward<C, false>(p, L, hd, valid, g_lp);
     SPP_TP(17);  // heads backward
     // ---- dh2 = Wh^T dheads * relu'(h2); dh1 = W2^T dh2 * relu'(h1)
-    dense<C::NB_PAIR, C::RV_PAIR, C::BF>(p.actor.WhT, 8, hd, nullptr, [&](int ob, const f32x16& acc) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int ur = 32 * ob + ru(q);
-        const float v = getbit(a2lo, a2hi, ob, q) ? acc[q] : 0.f;
-        L.bl[ur * 32] = v;
-        op_st<C::BF>(rsrc(p.AD2), ur, L.ld4, L.vo, v);
-      }
-    });
-    {
-      dense_lds<8, C::BF>(p.actor.W2T, big, nullptr, [&](int ob, const f32x16& acc) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          op_st<C::BF>(rsrc(p.AD1), 32 * ob + ru(q), L.ld4, L.vo, getbit(a1lo, a1hi, ob, q) ? acc[q] : 0.f);
-      });
-    }
+    actor_trunk_backward<C>(p, L, hd, a1lo, a1hi, a2lo, a2hi);
     SPP_TP(18);  // trunk backward
     const float ps = wave_sum(sac_part);
     const float pd = wave_sum(dist_part);
@@ -1196,25 +1270,8 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_heads(SacArgs p, AcmScratc
     const float g_lp = valid ? alpha * p.inv_B : 0.f;
     constexpr bool kWide = C::NB_PAIR > 2;
     if constexpr (SPLIT) {
-      // dca = 0; dca += critic 1's; dca += critic 2's, as the one-kernel phase sums them: there the critic
-      // that lost the min adds the exact +0 its zero delta2 gives.  Rows >= CA are not read by anything.
-      const int sel = z.SEL[L.b];
-      const rsrc_t r1 = rsrc_n(z.DCA[0], C::CA * L.ld4), r2 = rsrc_n(z.DCA[1], C::CA * L.ld4);
       f32x16 dca[C::NB_CA];
-#pragma unroll
-      for (int ib = 0; ib < C::NB_CA; ++ib)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int ur = 32 * ib + ru(q);
-          float v1 = 0.f, v2 = 0.f;
-          if (ur < C::CA) {  // (rows ur + 4h >= CA of the upper lane half read 0 through the bounded resource)
-            v1 = fm_ldb(r1, ur, L.ld4, L.vo);
-            v2 = fm_ldb(r2, ur, L.ld4, L.vo);
-          }
-          v1 = (sel & 1) ? v1 : 0.f;
-          v2 = (sel & 2) ? v2 : 0.f;
-          dca[ib][q] = fadd_rn(fadd_rn(0.f, v1), v2);
-        }
+      load_dca<C>(z, L, dca);
       SPP_TP(31);  // critics backward (here: its results read back)
       dca_to_dad<C, true>(p, z, L, small, dca);
       SPP_TP(16);  // ACM backward
@@ -1230,23 +1287,176 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_heads(SacArgs p, AcmScratc
     }
     SPP_TP(17);  // heads backward
     // ---- dh2 = Wh^T dheads * relu'(h2); dh1 = W2^T dh2 * relu'(h1)
-    dense<C::NB_PAIR, C::RV_PAIR, C::BF>(p.actor.WhT, 8, hd, nullptr, [&](int ob, const f32x16& acc) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int ur = 32 * ob + ru(q);
-        const float v = getbit(a2lo, a2hi, ob, q) ? acc[q] : 0.f;
-        L.bl[ur * 32] = v;
-        op_st<C::BF>(rsrc(p.AD2), ur, L.ld4, L.vo, v);
-      }
-    });
-    dense_lds<8, C::BF>(p.actor.W2T, big, nullptr, [&](int ob, const f32x16& acc) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q)
-        op_st<C::BF>(rsrc(p.AD1), 32 * ob + ru(q), L.ld4, L.vo, getbit(a1lo, a1hi, ob, q) ? acc[q] : 0.f);
-    });
+    actor_trunk_backward<C>(p, L, hd, a1lo, a1hi, a2lo, a2hi);
     SPP_TP(18);  // trunk backward
     const float pd = wave_sum(dist_part);
     if (lane == 0) p.part[tile * kParts + 3] = pd;
+  }
+  SPP_TP_FLUSH();
+}
+
+// ============================================================================ actor phase, stage split
+// k_sac_actor_heads<C, true> for narrow heads (NB_PAIR <= 2) cut in two at its hand-over point (the ADH rows):
+//
+//  k_sac_heads_stage      the per-sample stages: the chosen critics' gradients read back (z.SEL, z.DCA), the
+//                         frozen-ACM backward, the heads backward; d loss / d heads goes to ADH (as before: it is
+//                         the heads' weight-gradient operand) and the custom-loss partial to its slot.
+//  k_sac_actor_trunk_bwd  d loss / d heads read back from ADH into the pairing tile, the trunk's masks from
+//                         z.MASK, then Wh^T and W2^T with the AD2 / AD1 stores.
+//
+// The stages are libm transcendentals, three small dependent MFMA chains with LDS round trips between them and
+// HBM read-backs: latency, not MFMA issue.  In the phase kernel they run one wave per SIMD (its register file and
+// 32 KiB image) while the MFMA pipe idles.  The stage kernel keeps only what they touch (a per-wave image of
+// 16 NB_PAIR heads / a_d rows and the ACM's 64 rows, and a table of the limit / normaliser vectors: the host
+// passes an argument block whose table segments are those four, at offset 0), so several workgroups share a CU.
+// Both kernels call the phase kernel's device functions on the same values in the same order: every array is
+// bit-identical to k_sac_actor_heads<C, true>'s.
+//
+// The forward side of both phases is cut the same way, in three (ACT: the actor phase on S / EPS2 with the
+// operand, mask and Z stores; else the critic phase's target action on S2 / EPS1):
+//
+//  k_sac_trunk_fwd<C, ACT>      actor_trunk; the heads epilogue stores mu / raw log-std feature-major (ACT: to the
+//                               ADH rows, where the split forward kernel parks them; else to p.THD)
+//  k_sac_squash_stage<C, ACT>   the squash from those rows and eps, the ACM forward; the critics' action input
+//                               goes to p.SCA [CA][Bp] and log pi to p.SLP [Bp]
+//  k_sac_actor_phase<C, true, true> / k_sac_critic_phase<C, true>   the rest of the phase from S | SCA and SLP
+// floats: the ACM's three bias vectors (64 + 32 + 32) and actor_lim, acm_lim, n0, n1 (32 each: aout, ac <= 32)
+constexpr int kStageTab = 256;
+
+template <class C>
+__global__ __launch_bounds__(256, 2) void k_sac_heads_stage(SacArgs p, AcmScratch z) {
+  static_assert(C::NB_PAIR <= 2 && !C::BF, "narrow heads, fp32");
+  constexpr int HR = 16 * C::NB_PAIR;  // pairing rows j0 + 8h < 16 NB_PAIR; natural rows u + 4h < AOUT <= HR
+  constexpr int ROWS = HR + 64;        // + the ACM's SMALL image
+  __shared__ __attribute__((aligned(16))) float smem[kWavesPerWG * ROWS * 32];
+  __shared__ __attribute__((aligned(16))) float tbl[kStageTab];
+  SPP_TP_INIT();
+  load_table(p, tbl);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float* big = smem + w * ROWS * 32;
+  float* small = big + HR * 32;
+  const int ntiles = p.Bp / 32;
+  const int ld = p.Bp;
+  const float alpha = *p.alpha;
+  for (int tile = blockIdx.x * kWavesPerWG + w; tile < ntiles; tile += gridDim.x * kWavesPerWG) {
+    const Lane L = make_lane(big, small, tbl, ld, tile * 32 + (lane & 31));
+    const bool valid = L.b < p.B;
+    const float g_lp = valid ? alpha * p.inv_B : 0.f;
+    f32x16 dca[C::NB_CA];
+    load_dca<C>(z, L, dca);
+    SPP_TP(31);  // critics backward (here: its results read back)
+    dca_to_dad<C, true>(p, z, L, small, dca);
+    SPP_TP(16);  // ACM backward
+    f32x16 hd[C::NB_PAIR];
+    const float dist_part = heads_backward<C, true>(p, L, hd, valid, g_lp);
+    SPP_TP(17);  // heads backward
+    const float pd = wave_sum(dist_part);
+    if (lane == 0) p.part[tile * kParts + 3] = pd;
+  }
+  SPP_TP_FLUSH();
+}
+
+template <class C>
+__global__ __launch_bounds__(256, 1) void k_sac_actor_trunk_bwd(SacArgs p, AcmScratch z) {
+  static_assert(C::NB_PAIR <= 2 && !C::BF, "narrow heads, fp32");
+  __shared__ float smem[kWavesPerWG * kLdsPerWave];
+  SPP_TP_INIT();
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float* big = smem + w * kLdsPerWave;
+  float* small = big + kSmallRow * 32;
+  const int ntiles = p.Bp / 32;
+  const int ld = p.Bp;
+  for (int tile = blockIdx.x * kWavesPerWG + w; tile < ntiles; tile += gridDim.x * kWavesPerWG) {
+    const Lane L = make_lane(big, small, nullptr, ld, tile * 32 + (lane & 31));
+    const uint64_t* mk = z.MASK + (int64_t)tile * 4 * 64 + lane;
+    const uint64_t a1lo = mk[0], a1hi = mk[64], a2lo = mk[128], a2hi = mk[192];
+    // d loss / d heads at the pairing slots (heads_backward's stores); slots j >= AOUT hold 0, as its tile does
+    f32x16 hd[C::NB_PAIR];
+    load_pair_gl<C>(hd, p.ADH, L.ld4, L.vp);
+    SPP_TP(17);  // heads backward (here: its results read back)
+    actor_trunk_backward<C>(p, L, hd, a1lo, a1hi, a2lo, a2hi);
+    SPP_TP(18);  // trunk backward
+  }
+  SPP_TP_FLUSH();
+}
+
+template <class C, bool ACT>
+__global__ __launch_bounds__(256, 1) void k_sac_trunk_fwd(SacArgs p, AcmScratch z) {
+  static_assert(C::NB_PAIR <= 2 && !C::BF, "narrow heads, fp32");
+  __shared__ float smem[kWavesPerWG * kLdsPerWave];
+  __shared__ __attribute__((aligned(16))) float tbl[kTabMax];
+  SPP_TP_INIT();
+  load_table(p, tbl);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float* big = smem + w * kLdsPerWave;
+  float* small = big + kSmallRow * 32;
+  const int ntiles = p.Bp / 32;
+  const int ld = p.Bp;
+  for (int tile = blockIdx.x * kWavesPerWG + w; tile < ntiles; tile += gridDim.x * kWavesPerWG) {
+    const Lane L = make_lane(big, small, tbl, ld, tile * 32 + (lane & 31));
+    uint64_t a1lo = 0, a1hi = 0, a2lo = 0, a2hi = 0;
+    SPP_TP(ACT ? 26 : 0);
+    if constexpr (ACT) {
+      actor_trunk<C, true, C::NB_H2, 2 * C::AOUT, true>(p.actor, p.S, C::OB * L.ld4, L, p.AH1, p.AH2, a1lo, a1hi, a2lo,
+                                                        a2hi, p.ADH);
+      uint64_t* mk = z.MASK + (int64_t)tile * 4 * 64 + lane;
+      mk[0] = a1lo;
+      mk[64] = a1hi;
+      mk[128] = a2lo;
+      mk[192] = a2hi;
+      SPP_TP(27);  // actor trunk
+    } else {
+      actor_trunk<C, false, C::NB_H2, 2 * C::AOUT, true>(p.actor, p.S2, C::OB * L.ld4, L, nullptr, nullptr, a1lo, a1hi,
+                                                         a2lo, a2hi, p.THD);
+    }
+  }
+  SPP_TP_FLUSH();
+}
+
+template <class C, bool ACT>
+__global__ __launch_bounds__(256, 2) void k_sac_squash_stage(SacArgs p, AcmScratch z) {
+  static_assert(C::NB_PAIR <= 2 && !C::BF, "narrow heads, fp32");
+  constexpr int HR = 16 * C::NB_PAIR;  // (as k_sac_heads_stage)
+  constexpr int ROWS = HR + 64;
+  __shared__ __attribute__((aligned(16))) float smem[kWavesPerWG * ROWS * 32];
+  __shared__ __attribute__((aligned(16))) float tbl[kStageTab];
+  SPP_TP_INIT();
+  load_table(p, tbl);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float* big = smem + w * ROWS * 32;
+  float* small = big + HR * 32;
+  const int ntiles = p.Bp / 32;
+  const int ld = p.Bp;
+  const float* X = ACT ? p.S : p.S2;
+  for (int tile = blockIdx.x * kWavesPerWG + w; tile < ntiles; tile += gridDim.x * kWavesPerWG) {
+    const Lane L = make_lane(big, small, tbl, ld, tile * 32 + (lane & 31));
+    SPP_TP(ACT ? 26 : 0);
+    f32x16 hd[C::NB_PAIR];
+    load_pair_gl<C>(hd, ACT ? p.ADH : p.THD, L.ld4, L.vp);
+    // (the critic phase squashes branch-free, the actor phase with the per-slot branches: as the phase kernels)
+    const float lp = squash_write<C, !ACT>(p, hd, ACT ? p.EPS2 : p.EPS1, L);  // a_d -> big rows [0, AOUT)
+    SPP_TP(ACT ? 28 : 4);  // squash
+    if constexpr (C::ACMC) {
+      f32x16 xin[C::NB_ACMIN];
+      load_cat_gl<C::NB_OB, C::NB_AOUT>(xin, X, C::OB * L.ld4, C::OB, L.ld4, L.vo, big, C::AOUT);
+      acm_forward<C, ACT>(p, xin, L, z.Z1, z.Z2, z.T3);
+    }
+    // the critics' action input, natural layout: c from SMALL rows [0, AC) (this lane's own stores), or a_d from
+    // the image rows [0, AOUT) (written in the pairing layout: other lanes' rows)
+    SPP_XLANE_SYNC();
+    const float* src = C::ACMC ? L.sl : L.bl;
+    const rsrc_t cr = rsrc(p.SCA);
+#pragma unroll
+    for (int ib = 0; ib < C::NB_CA; ++ib)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int ur = 32 * ib + ru(q);
+        if (ur < C::CA) {
+          if (ur + L.h4 < C::CA) fm_st(cr, ur, L.ld4, L.vo, src[ur * 32]);
+        }
+      }
+    if (L.h == 0) p.SLP[L.b] = lp;
+    SPP_TP(ACT ? 29 : 5);  // ACM forward
   }
   SPP_TP_FLUSH();
 }

@@ -63,6 +63,10 @@ struct SacArgs {
   // actor-phase outputs
   float *AH1, *AH2, *AD1, *AD2, *ADH;
   float *part;  // per-tile partial sums [ntiles][8]
+  // stage split hand-overs (sac.hip; feature-major, written once and read once at the sample's own column): the
+  // target actor heads [2 aout][Bp] (the actor phase's go to ADH), and, shared by the two phases, the critics'
+  // action input [CA][Bp] and log pi [Bp]
+  float *THD, *SCA, *SLP;
   // SAC critic phase: per-wave partials of the fused fc3 weight gradient, [waves][w3p_stride] per critic
   float* W3P[2];
   int64_t w3p_stride;

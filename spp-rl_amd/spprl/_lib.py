@@ -114,6 +114,7 @@ _SIGS = {
     "sppReplaySetAcmColumns": (c_int, [c_void_p, c_void_p, c_int]),
     "sppAgentSetTiming": (c_int, [c_void_p, c_int]),
     "sppAgentGetTiming": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "sppAgentStageSplit": (c_int, [c_void_p, P(c_int)]),
     "sppSynthEnvStep": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sppDdpgAcmUpdate": (c_int, [c_void_p, P(Batch), c_void_p, c_void_p]),
     "sppDdpgAcmCriticGrads": (c_int, [c_void_p, P(Batch), c_void_p, c_void_p]),

@@ -16,7 +16,12 @@ from spprl import _lib  # noqa: E402
 # Kernel sets built with the register hand-over (SPP_GEN_INPUTS, csrc/common.h; the fp32 narrow-input sets) produce
 # the critics' fc1 output and delta2 inside the consumer layer: the "L1" regions then hold only the first fragment
 # request, the "delta staging" regions nothing, and their work is counted in the following L2 / W2T region.
-NAMES = {0: "tile start", 1: "actor L1", 2: "actor L2", 3: "actor heads", 4: "squash", 5: "ACM + target input",
+# With the stage split (SPP_STAGE_SPLIT, csrc/sac.hip) the slots keep their stages and name the kernel that now runs them:
+# T = k_sac_trunk_fwd, S = k_sac_squash_stage / k_sac_heads_stage (3 workgroups per CU: a slot's cycles are the
+# wave's own, while two other waves share its SIMD), R = the rest kernels (k_sac_critic_phase<C, true>,
+# k_sac_actor_phase<C, true, true>, k_sac_actor_trunk_bwd), whose "tile start" slots hold the hand-over read-backs.
+NAMES = {0: "tile start (R: + SCA / SLP read-back)", 1: "actor L1 (T)", 2: "actor L2 (T)", 3: "actor heads (T: -> THD)",
+         4: "squash (S: + THD read-back)", 5: "ACM + target input (S: -> SCA / SLP)",
          6: "targ1 L1 (gen: request only)", 7: "targ1 L2 (gen: + L1)", 8: "targ2 L1 (gen: request only)",
          9: "targ2 L2 (gen: + L1)", 10: "y + critic input", 11: "critic L1 (gen: request only)",
          12: "critic L2 (gen: + L1)", 13: "delta2 staging (gen: fc3 gradient only)", 14: "critic W2T (gen: + delta2)",
@@ -26,9 +31,11 @@ NAMES = {0: "tile start", 1: "actor L1", 2: "actor L2", 3: "actor heads", 4: "sq
          22: "dense_lds epilogue | A: W1Ta (nodense)",
          23: "dense prologue | A: ACM bwd input (nodense)", 24: "dense mfma | A: ACM W3T (nodense)",
          25: "dense epilogue | A: ACM W2T (nodense)",
-         26: "A: tile start", 27: "A: actor trunk", 28: "A: squash", 29: "A: ACM fwd", 19: "A: q min",
-         30: "A: critics L1 (fwd; gen: request only)", 31: "A: critics L2 (fwd; gen: + L1)", 16: "A: ACM bwd",
-         17: "A: heads bwd", 18: "A: trunk bwd"}
+         26: "A: tile start (R: + SCA / SLP read-back)", 27: "A: actor trunk (T: -> ADH, MASK)",
+         28: "A: squash (S: + ADH read-back)", 29: "A: ACM fwd (S: -> SCA / SLP)", 19: "A: q min",
+         30: "A: critics L1 (fwd; gen: request only)",
+         31: "A: critics L2 (fwd; gen: + L1) | DCA read-back (S)", 16: "A: ACM bwd (S)",
+         17: "A: heads bwd (S) | ADH read-back (R)", 18: "A: trunk bwd (R)"}
 
 
 def main():
