@@ -24,23 +24,23 @@ Where the kernels convert (spp-rl_amd/csrc; "R(.)" = one RNE fp32 -> bf16, every
     gradient sums the A rows it read: R(delta) for bf16 rows (sum_bf8 dw.hip:57-65,115), the fp32 delta for
     fp32 rows (dw.hip:117-118).
 
-  matmul of the update                     forward / data-gradient operands        weight-gradient (k_dw job, api.hip)
+  matmul of the update                     forward / data-gradient operands        weight-gradient (k_dw job; csrc/api.hip)
   ---------------------------------------  --------------------------------------  -------------------------------------
-  actor fc1      (target a', and a)        R(s) R(W1)          sac.hip:260          R(AD1) R(s)^T, db = sum R(AD1)  api.hip:1298
-  actor fc2                                R(h1) R(W2)         sac.hip:276          R(AD2) R(AH1)^T, sum R(AD2)     api.hip:1299
-  actor fc_prob | fc_scale                 R(h2) R(Wh)         sac.hip:291          R(ADH) R(AH2)^T, db = sum ADH   api.hip:1300
+  actor fc1      (target a', and a)        R(s) R(W1)          sac.hip:260          R(AD1) R(s)^T, db = sum R(AD1)  api.hip build_dw
+  actor fc2                                R(h1) R(W2)         sac.hip:276          R(AD2) R(AH1)^T, sum R(AD2)     api.hip build_dw
+  actor fc_prob | fc_scale                 R(h2) R(Wh)         sac.hip:291          R(ADH) R(AH2)^T, db = sum ADH   api.hip build_dw
     (two-tile target pass: sac_bf.h:272,281,291; bias added in fp32 sac_bf.h:301-302)
   actor heads^T . d heads                  R(ADH) R(Wh)        sac.hip:861,994      (delta AD2 = relu' . acc, op_st sac.hip:867,1000)
   actor W2^T . AD2                         R(AD2) R(W2)        sac.hip:871,1003     (delta AD1, op_st sac.hip:874,1006)
   ACM fc1 / fc2 / fc3 (frozen)             R(in) R(W)          sac.hip:309,320,336  none (z1, z2, t3 stay fp32: fm_st sac.hip:315,325,343)
   ACM W3^T / W2^T / W1a^T . delta          R(delta) R(W)       sac.hip:729,739,749  none
   critic / target fc1                      R([s|c]) R(W1)      sac.hip:358, sac_bf.h:248,254,345,389
-                                                                                    R(D1) R([s|a])^T, sum R(D1)     api.hip:1281
+                                                                                    R(D1) R([s|a])^T, sum R(D1)     api.hip critic_dw
   critic / target fc2                      R(h1) R(W2)         sac.hip:373, sac_bf.h:357,413
-                                                                                    R(D2) R(H1)^T, sum R(D2)        api.hip:1282
+                                                                                    R(D2) R(H1)^T, sum R(D2)        api.hip critic_dw
   critic / target fc3                      fp32: q = w3 . h2 + b3, fmaf over the table's fp32 w3
                                            sac.hip:382,388, sac_bf.h:361,365,423,434
-                                                                                    R(DQ) R(H2)^T, db = sum DQ      api.hip:1284
+                                                                                    R(DQ) R(H2)^T, db = sum DQ      api.hip critic_dw
                                                                                     (bf16 sets build with SPP_BF16_FUSE3 = 0:
                                                                                     fc3 is a k_dw job, not fused, common.h:20)
   critic delta2 = dq w3 relu'(h2)          fp32 product        sac.hip:547,674, sac_bf.h:454

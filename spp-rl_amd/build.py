@@ -1,8 +1,10 @@
 """Build libspprl.so (gfx950) in-tree with hipcc.  Usage: python spp-rl_amd/build.py [--force]
 
-The library is one api.hip translation unit (C-ABI, non-template kernels) plus one
-translation unit per phase-kernel config family (csrc/ks_*.hip); they compile in
-parallel into build/ and link into spp-rl_amd/spprl/libspprl.so.
+The library is two C-ABI units (csrc/api.hip, and csrc/api_onp.hip with the on-policy handle and its non-template
+kernels) plus one unit per phase-kernel config family (csrc/ks_*.hip); they compile in parallel into build/ and
+link into spp-rl_amd/spprl/libspprl.so.  Every compile writes a depfile (build/<unit>.o.d): a unit is recompiled
+when its object is older than any file the compiler read for it.  --prof builds api.hip, which then includes
+api_onp.hip and the kernel sets, as one unit into libspprl_prof.so.
 """
 import glob
 import os
@@ -24,8 +26,11 @@ def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*"))) + [os.path.join(REPO, "include", "spprl.h")]
 
 
+API_UNITS = ("api.hip", "api_onp.hip")  # by name: no other api*.hip file is ever compiled or linked
+
+
 def units():
-    return [os.path.join(CSRC, "api.hip")] + sorted(glob.glob(os.path.join(CSRC, "ks_*.hip")))
+    return [os.path.join(CSRC, u) for u in API_UNITS] + sorted(glob.glob(os.path.join(CSRC, "ks_*.hip")))
 
 
 def up_to_date():
@@ -35,29 +40,62 @@ def up_to_date():
     return all(os.path.getmtime(s) <= t for s in sources())
 
 
-KSET_DEPS = ("kset.h", "sac.hip", "sac_team.h", "ddpg.hip", "ddpg_team.h", "sac_kernels.h", "mlp.h", "common.h")
-
-
 def _obj(src):
     return os.path.join(OBJ, os.path.basename(src).replace(".hip", ".o"))
 
 
+def parse_depfile(text):
+    """The prerequisites of a make rule as the compiler writes it (-MD): `target: dep dep \\<newline> dep ...`,
+    a space inside a path escaped as `\\ `.  None when the text is no such rule."""
+    text = text.replace("\\\n", " ")
+    words, cur, i = [], "", 0
+    while i < len(text):
+        c = text[i]
+        if c == "\\" and i + 1 < len(text) and text[i + 1] in " #\\":
+            cur += text[i + 1]
+            i += 2
+            continue
+        if c == "$" and text[i + 1:i + 2] == "$":
+            cur += "$"
+            i += 2
+            continue
+        if c.isspace():
+            if cur:
+                words.append(cur)
+            cur = ""
+        else:
+            cur += c
+        i += 1
+    if cur:
+        words.append(cur)
+    if not words or not words[0].endswith(":"):
+        return None
+    return words[1:]
+
+
 def _stale(src):
-    """api.hip depends on every csrc file; ks_*.hip only on the phase-kernel headers."""
+    """True unless the unit's object is newer than every file its depfile lists (system headers included: a
+    ROCm upgrade is a reason to rebuild).  A missing or unreadable depfile, or a listed file that is gone, is stale."""
     obj = _obj(src)
-    if not os.path.exists(obj):
+    try:
+        t = os.path.getmtime(obj)
+        with open(obj + ".d") as f:
+            deps = parse_depfile(f.read())
+        if not deps:
+            return True
+        return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in deps)
+    except OSError:
         return True
-    if os.path.basename(src) == "ks_dw.hip":
-        deps = [src] + [os.path.join(CSRC, d) for d in ("dw.hip", "internal.h", "common.h", "mlp.h")]
-    elif os.path.basename(src).startswith("ks_"):
-        deps = [src] + [os.path.join(CSRC, d) for d in KSET_DEPS]
-    else:
-        deps = [f for f in glob.glob(os.path.join(CSRC, "*")) if not os.path.basename(f).startswith("ks_")]
-    deps.append(os.path.join(REPO, "include", "spprl.h"))
-    t = os.path.getmtime(obj)
-    return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _jobs(n):
+    """Parallel compiles: MAX_JOBS, else CMAKE_BUILD_PARALLEL_LEVEL, else 8; at most 16 and at most n."""
+    want = 8
+    for var in ("MAX_JOBS", "CMAKE_BUILD_PARALLEL_LEVEL"):
+        if os.environ.get(var, "").isdigit():
+            want = int(os.environ[var])
+            break
+    return max(1, min(want, 16, n))
 
 
 def _resources(text):
@@ -82,9 +120,9 @@ def _resources(text):
 
 def _compile(src, verbose):
     obj = _obj(src)
-    cmd = [HIPCC] + FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", obj, src]
+    cmd = [HIPCC] + FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-MD", "-MF", obj + ".d", "-c", "-o", obj, src]
     t0 = time.time()
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=CSRC)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed on %s:\n%s" % (src, r.stdout[-8000:]))
     os.utime(obj, (t0, t0))  # stamped with the compile's start: a source edited meanwhile stays newer
@@ -160,10 +198,10 @@ def build(force=False, verbose=True, prof=False, hopper_only=False, jobs=None, n
     os.makedirs(OBJ, exist_ok=True)
     t0 = time.time()  # the library is stamped with this time: a source edited during the build stays newer
     srcs = units()
-    jobs = jobs or min(len(srcs), max(1, min(os.cpu_count() or 1, 8)))
-    if verbose:
-        print("hipcc %s  (%d units, %d jobs)" % (" ".join(FLAGS), len(srcs), jobs), flush=True)
     todo = [s for s in srcs if force or _stale(s)]
+    jobs = jobs or _jobs(len(todo))
+    if verbose:
+        print("hipcc %s  (%d of %d units, %d jobs)" % (" ".join(FLAGS), len(todo), len(srcs), jobs), flush=True)
     with ThreadPoolExecutor(jobs) as ex:
         list(ex.map(lambda s: _compile(s, verbose), todo))
     objs = [_obj(s) for s in srcs]

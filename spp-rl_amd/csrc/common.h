@@ -134,6 +134,9 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// log sqrt(2 pi) of the on-policy Gaussian log-densities (onp*.hip, sgd_mlp.hip)
+constexpr float kLogSqrt2PiO = 0.91893853320467274178f;
+
 // ---------------------------------------------------------------- Philox4x32-10
 struct u32x4 { uint32_t x, y, z, w; };
 __host__ __device__ __forceinline__ u32x4 philox(uint64_t key64, uint64_t ctr_hi, uint64_t ctr_lo) {

@@ -10,6 +10,7 @@
 //                     (ppo.py:174-190, 194-204; on_policy.py:189-205)
 //  k_onp_act          a ~ Normal(mu, sigma) (or mu), log_prob (basic_model.py:32-51)
 // Per-wave LDS image rows: hidden tiles at rows [0, 64).
+#include "block_sum.h"
 #include "sac_kernels.h"
 
 namespace spp {
@@ -22,7 +23,6 @@ struct OCfg {
   static constexpr uint64_t RV_H = rv_nat(64, 2);
   static constexpr uint64_t RV_AOUT = rv_nat(AOUT, NB_AOUT);
 };
-constexpr float kLogSqrt2PiO = 0.91893853320467274178f;
 
 struct OnpNet {
   const float4 *W1, *W2, *W3, *W3T, *W2T;  // W3T / W2T: backward images

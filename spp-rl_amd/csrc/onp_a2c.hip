@@ -5,7 +5,7 @@
 //  k_onp_pg_actor_grad  A2C.update_actor's backward (a2c.py:267-286; on_policy.py:100-124): k_onp_actor_grad's
 //                       forward, log-prob and backward with the objective -logp * A / N, A normalised on the fly
 //                       with A2C's (adv - mean) / (std + 1e-8)
-// (included by api.hip after onp.hip and ppo.hip: OnpArgs, onp_trunk, ppo_q)
+// (included by api_onp.hip after onp.hip and ppo.hip: OnpArgs, onp_trunk, ppo_q)
 
 namespace spp {
 

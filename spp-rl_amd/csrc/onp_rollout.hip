@@ -12,10 +12,10 @@
 //  k_onp_obs_stats    Memory.update_obs_mean_std: column mean and ddof-1 std over the iteration's observations
 //                     (each rollout's first observation + every next observation) in fp64, blended into the running
 //                     mean / std, and the exact 1st / 99th np.percentile of the frames' obs rows by a 4-pass 8-bit
-//                     radix select per order statistic (fkey / funkey, replay.hip), max / min into the running pair.
+//                     radix select per order statistic (fkey / funkey, replay.h), max / min into the running pair.
 //                     One workgroup per column; plain [rows][ob] arrays.
 #pragma once
-// (included by api.hip after replay.hip and onp.hip: obs_norm1, fkey / funkey, philox, kLogSqrt2PiO)
+// (included by api_onp.hip after onp.hip; obs_norm1, fkey / funkey: replay.h; philox, kLogSqrt2PiO: common.h)
 #include "layout.h"
 
 namespace spp {

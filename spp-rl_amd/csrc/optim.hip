@@ -3,6 +3,7 @@
 //   Adam      torch.optim.Adam single-tensor step (rltoolkit/rl.py:62)
 //   polyak    rltoolkit/algorithms/sac/sac.py:186-199 (mul_ then add_, two roundings)
 //   alpha     sac.py:201-216 + sac_acm.py:153-159 (log_alpha is float64)
+#include "block_sum.h"
 #include "internal.h"
 
 namespace spp {
@@ -129,21 +130,7 @@ __global__ void k_adam(const AdamJob* __restrict__ jobs, float neg_step, float b
   }
 }
 
-// Deterministic block reduction of per-tile partial sums (double accumulate).
-__device__ double block_sum(const float* part, int ntiles, int stride, int slot) {
-  __shared__ double red[256];
-  double s = 0.0;
-  for (int t = threadIdx.x; t < ntiles; t += blockDim.x) s += (double)part[(int64_t)t * stride + slot];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
+// (block_sum, the one-slot block reduction of per-tile partials: block_sum.h)
 
 // NS consecutive partial slots [slot0, slot0 + NS) of every tile summed in ONE pass by kFinThreads
 // threads (several tiles' loads in flight per thread), then one fixed-order LDS tree per slot:

@@ -27,4 +27,30 @@ constexpr int kRecAcm = 4;  // first ACM word
 __host__ __device__ inline int rec_words(int aout, int ac) { return (kRecAcm + ac + aout + 15) / 16 * 16; }
 __host__ __device__ inline int rec_act(const ReplayDev& r) { return kRecAcm + r.ac; }  // first action word
 
+// Device helpers that the on-policy kernels (onp_rollout.hip) share with replay.hip / stats.hip.
+// fkey(): the order-preserving uint32 image of a float (the radix selects' keys); funkey(): its inverse.
+__device__ __forceinline__ uint32_t fkey(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float funkey(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// MemoryMeta.normalize / denormalize (rltoolkit/buffer/memory.py:76-127) elementwise
+// over [rows][ob], the same fp32 operation order as the fused device helpers:
+//   min-max : (x - mid) / (hi - mid + 1e-8)     |  mid + x * (hi - lo) / 2
+//   z-score : clamp((x - mean) / (std + 1e-8), -10, 10)  |  (std + 1e-8) * x + mean
+__device__ __forceinline__ float obs_norm1(float v, int j, const float* lo, const float* hi, const float* mean,
+                                           const float* std, int min_max, int inverse) {
+  if (min_max) {
+    const float l = lo[j], h = hi[j];
+    const float mid = fadd_rn(h, l) * 0.5f;
+    return inverse ? fadd_rn(mid, fmul_rn(v, fsub_rn(h, l) * 0.5f))
+                   : fdiv_rn(fsub_rn(v, mid), fadd_rn(fsub_rn(h, mid), 1e-8f));
+  }
+  return inverse ? fadd_rn(fmul_rn(fadd_rn(std[j], 1e-8f), v), mean[j])
+                 : fminf(fmaxf(fdiv_rn(fsub_rn(v, mean[j]), fadd_rn(std[j], 1e-8f)), -10.f), 10.f);
+}
+
 }  // namespace spp

@@ -284,14 +284,7 @@ __global__ __launch_bounds__(256) void k_replay_gather_acm(ReplayDev r, const in
 }
 
 // ---------------------------------------------------------------- obs statistics
-// update_obs_mean_std (:83-96) over X = obs[obs_idx[0:len)]
-__device__ __forceinline__ uint32_t fkey(float x) {
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float funkey(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+// update_obs_mean_std (:83-96) over X = obs[obs_idx[0:len)]  (the keys fkey / funkey: replay.h)
 
 // Exact order statistics by 4-pass 8-bit radix select over the fp32 keys, for the
 // 4 ranks of each column: lo / hi of the 99th percentile, lo / hi of the 1st.
@@ -698,22 +691,7 @@ __global__ void k_synth_reset(float* obs, const uint8_t* mask, int E, int ob, ui
 }
 
 
-// MemoryMeta.normalize / denormalize (rltoolkit/buffer/memory.py:76-127) elementwise
-// over [rows][ob], the same fp32 operation order as the fused device helpers:
-//   min-max : (x - mid) / (hi - mid + 1e-8)     |  mid + x * (hi - lo) / 2
-//   z-score : clamp((x - mean) / (std + 1e-8), -10, 10)  |  (std + 1e-8) * x + mean
-__device__ __forceinline__ float obs_norm1(float v, int j, const float* lo, const float* hi, const float* mean,
-                                           const float* std, int min_max, int inverse) {
-  if (min_max) {
-    const float l = lo[j], h = hi[j];
-    const float mid = fadd_rn(h, l) * 0.5f;
-    return inverse ? fadd_rn(mid, fmul_rn(v, fsub_rn(h, l) * 0.5f))
-                   : fdiv_rn(fsub_rn(v, mid), fadd_rn(fsub_rn(h, mid), 1e-8f));
-  }
-  return inverse ? fadd_rn(fmul_rn(fadd_rn(std[j], 1e-8f), v), mean[j])
-                 : fminf(fmaxf(fdiv_rn(fsub_rn(v, mean[j]), fadd_rn(std[j], 1e-8f)), -10.f), 10.f);
-}
-
+// MemoryMeta.normalize / denormalize elementwise over [rows][ob] (obs_norm1, replay.h)
 __global__ void k_obs_normalize(const float* __restrict__ x, int64_t n, int ob, const float* lo, const float* hi,
                                 const float* mean, const float* std, int min_max, int inverse, float* out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

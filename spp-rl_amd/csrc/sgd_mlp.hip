@@ -36,7 +36,7 @@
 // data-parallel replica running the same launch) holds identical parameters.
 // Adam follows torch.optim.Adam's operation order (IEEE divide / sqrt), as k_adam.
 #pragma once
-// (included by api.hip after sgd.hip: the slab helpers and the bounded arrival barrier)
+// (included through host.h after sgd.hip: the slab helpers and the bounded arrival barrier)
 
 namespace spp {
 

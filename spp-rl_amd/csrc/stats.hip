@@ -25,7 +25,7 @@
 //                 next call.  A rank outside the bracket (a sample miss) falls back to a radix
 //                 select over the column's raw data; more candidates than the LDS holds are
 //                 visited in the global lists: the result is exact in every case.
-// Keys: fkey() is the order-preserving uint32 image of a float (replay.hip).
+// Keys: fkey() is the order-preserving uint32 image of a float (replay.h).
 #pragma once
 #include "replay.h"
 

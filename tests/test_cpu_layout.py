@@ -20,7 +20,7 @@ CSRC = os.path.join(REPO, "spp-rl_amd", "csrc")
 # 3-dim test set, each with the critic on the actor output or on the ACM action, and the vanilla shapes
 AGENT_DIMS = [(11, 11, 3, False), (11, 11, 3, True), (17, 17, 6, False), (17, 17, 6, True),
               (111, 111, 8, False), (111, 111, 8, True), (3, 3, 1, False), (3, 3, 1, True), (17, 6, 6, False)]
-# (ob, aout) of every on-policy instantiation (find_onp, csrc/api.hip)
+# (ob, aout) of every on-policy instantiation (find_onp, csrc/api_onp.hip)
 ONP_DIMS = [(17, 17), (11, 11), (17, 6), (11, 3), (3, 1)]
 
 
@@ -75,7 +75,7 @@ def test_written_dims_are_the_instantiated_ones():
         for o, a, c in re.findall(r"= make_d?kset<(\d+), (\d+), (\d+), false>\(\)", txt):
             ks.add((int(o), int(a), int(c), False))
     assert ks == set(AGENT_DIMS)
-    onp = re.findall(r"make_onp<(\d+), (\d+)>\(\)", open(os.path.join(CSRC, "api.hip")).read())
+    onp = re.findall(r"make_onp<(\d+), (\d+)>\(\)", open(os.path.join(CSRC, "api_onp.hip")).read())
     assert {(int(o), int(a)) for o, a in onp} == set(ONP_DIMS)
 
 

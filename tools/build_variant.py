@@ -1,6 +1,6 @@
 """Build an A/B variant of libspprl.so with extra compile definitions (never the default library).
 
-    python tools/build_variant.py TAG [--only=ks_dw.hip,...] -DNAME=VALUE ...   ->  spp-rl_amd/spprl/libspprl_TAG.so
+    python tools/build_variant.py TAG [--only=api_onp.hip,ks_dw.hip,...] -DNAME=VALUE ...   ->  spp-rl_amd/spprl/libspprl_TAG.so
 
 --only compiles just the named units with the definitions and links the default build's objects
 for the rest.
