@@ -365,6 +365,11 @@ sppStatus sppAgentSetTiming(sppAgentHandle h, int enable);
 /* Which cuts of the SAC phases' stage split this handle runs (bit 0: the actor backward's per-sample stages as
  * their own kernel); 0 for handles whose shapes have none, or under SPP_STAGE_SPLIT=0 (read at creation). */
 sppStatus sppAgentStageSplit(sppAgentHandle h, int* bits_out);
+/* Which SAC phase kernels of this handle split a tile's two critics over a pair of waves (bit 0: the critic phase
+ * behind stage-split cut 3, bit 1: the actor phase's critics behind cut 2); 0 for handles without those cuts, or
+ * under SPP_CRITIC_PAIRS=0 (read at creation; the default is 1, and 3 asks for both).  The small-batch team
+ * kernels are not paired. */
+sppStatus sppAgentCriticPairs(sppAgentHandle h, int* bits_out);
 sppStatus sppAgentGetTiming(sppAgentHandle h, double* ms_out /*[5]*/, int64_t* count_out /*[5]*/);
 
 /* Rollout action (rltoolkit/acm/off_policy/ddpg_acm.py:40-50 noise_action +

@@ -778,6 +778,10 @@ struct sppAgent {
   //   bit 1  k_sac_actor_phase<C, true> -> k_sac_trunk_fwd<C, true>, k_sac_squash_stage<C, true>, the critics
   //   bit 2  k_sac_critic_phase         -> k_sac_trunk_fwd<C, false>, k_sac_squash_stage<C, false>, the rest
   int stage_split = 0;
+  // wave pairs over a tile's two critics (sac.hip), one bit per kernel; SPP_CRITIC_PAIRS=0: the unpaired kernels (A/B).
+  //   bit 0  k_sac_critic_phase<C, true>      -> <C, true, true>        (behind stage-split cut 3)
+  //   bit 1  k_sac_actor_phase<C, true, true> -> <C, true, true, true>  (behind stage-split cut 2)
+  int critic_pairs = 0;
   float *THD = nullptr, *SCA = nullptr, *SLP = nullptr;  // its hand-overs (SacArgs)
   AcmScratch mq{};  // its hand-over buffers (SEL ... DCA)
   // ACM regression scratch
@@ -1239,6 +1243,7 @@ static void launch_adam(sppAgent* a, int first, int count, int64_t n, int64_t st
 constexpr int kStageWGPerCU = 3;
 constexpr int kStageSplitAll = 7;
 constexpr int kStageSplitDefault = kStageSplitAll;
+constexpr int kCriticPairsDefault = 1;  // bit 1 measured inside the run-to-run range: off unless asked for
 static int stage_grid(sppAgent* a, int Bp) {
   return std::max(1, std::min(cdiv(Bp / 32, kWavesPerWG), kStageWGPerCU * a->num_cu));
 }
@@ -1365,6 +1370,10 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
     const bool have = ks.heads_stage && ks.trunk_bwd && ks.trunk_fwd_a && ks.squash_a && ks.critics_a &&
                       ks.trunk_fwd_c && ks.squash_c && ks.critic_rest;
     if (a->minq_split && have && tab_fits) a->stage_split = want & kStageSplitAll;
+    const char* cp = getenv("SPP_CRITIC_PAIRS");
+    const int wantp = cp ? atoi(cp) : kCriticPairsDefault;
+    if ((a->stage_split & 4) && ks.critic_rest_pair) a->critic_pairs |= wantp & 1;
+    if ((a->stage_split & 2) && ks.critics_a_pair) a->critic_pairs |= wantp & 2;
   }
   const int ob = cfg->ob, aout = cfg->aout, ac = cfg->ac;
   a->cin = ob + (cfg->acm_critic ? ac : aout);
@@ -1570,7 +1579,7 @@ static sppStatus critic_grads_staged(sppAgentHandle a, float* losses, hipStream_
     // stage split: the target actor's trunk; the squash and the ACM forward; both target critics and the critics
     hipLaunchKernelGGL(a->ks.trunk_fwd_c, dim3(tile_grid(a, p.Bp)), dim3(256), 0, st, p, a->mq);
     hipLaunchKernelGGL(a->ks.squash_c, dim3(stage_grid(a, p.Bp)), dim3(256), 0, st, stage_args(a, p), a->mq);
-    hipLaunchKernelGGL(a->ks.critic_rest, dim3(grid), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((a->critic_pairs & 1) ? a->ks.critic_rest_pair : a->ks.critic_rest, dim3(grid), dim3(256), 0, st, p);
   } else {
     hipLaunchKernelGGL(team ? a->ks.critic_team : a->ks.critic, dim3(grid), dim3(team ? 64 * kTeamCritic : 256), 0, st, p);
   }
@@ -1627,7 +1636,7 @@ static sppStatus actor_grads(sppAgentHandle a, float* losses, hipStream_t st) {
     if (a->stage_split & 2) {
       hipLaunchKernelGGL(a->ks.trunk_fwd_a, dim3(grid), dim3(256), 0, st, p, z);
       hipLaunchKernelGGL(a->ks.squash_a, dim3(stage_grid(a, p.Bp)), dim3(256), 0, st, stage_args(a, p), z);
-      hipLaunchKernelGGL(a->ks.critics_a, dim3(grid), dim3(256), 0, st, p, z);
+      hipLaunchKernelGGL((a->critic_pairs & 2) ? a->ks.critics_a_pair : a->ks.critics_a, dim3(grid), dim3(256), 0, st, p, z);
     } else {
       hipLaunchKernelGGL(a->ks.actor_fwd, dim3(grid), dim3(256), 0, st, p, z);
     }
@@ -1671,6 +1680,12 @@ sppStatus sppSacAcmActorGrads(sppAgentHandle a, const float* eps_cur, float* los
 sppStatus sppAgentStageSplit(sppAgentHandle a, int* bits_out) {
   SPP_REQUIRE(a && bits_out, SPP_E_INVALID_ARG, "null");
   *bits_out = a->stage_split;
+  return SPP_OK;
+}
+
+sppStatus sppAgentCriticPairs(sppAgentHandle a, int* bits_out) {
+  SPP_REQUIRE(a && bits_out, SPP_E_INVALID_ARG, "null");
+  *bits_out = a->critic_pairs;
   return SPP_OK;
 }
 

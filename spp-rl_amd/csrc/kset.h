@@ -46,6 +46,9 @@ struct KernelSet {
   void (*trunk_fwd_c)(SacArgs, AcmScratch);
   void (*squash_c)(SacArgs, AcmScratch);
   void (*critic_rest)(SacArgs);
+  // wave-pair forms of critics_a and critic_rest (sac.hip): a tile's two critics on two waves
+  void (*critics_a_pair)(SacArgs, AcmScratch);
+  void (*critic_rest_pair)(SacArgs);
 };
 
 template <int OB, int AOUT, int AC, bool ACMC, bool BF = false>
@@ -72,6 +75,8 @@ KernelSet make_kset() {
       ks.trunk_fwd_c = k_sac_trunk_fwd<C, false>;
       ks.squash_c = k_sac_squash_stage<C, false>;
       ks.critic_rest = k_sac_critic_phase<C, true>;
+      ks.critics_a_pair = k_sac_actor_phase<C, true, true, true>;
+      ks.critic_rest_pair = k_sac_critic_phase<C, true, true>;
     }
   }
   return ks;

@@ -572,11 +572,42 @@ __device__ __forceinline__ float squash_write(const SacArgs& p, const f32x16 (&h
   return fsub_rn(tot, tc);
 }
 
+// ============================================================================ wave pairs
+// PAIR forms of the phase kernels (k_sac_critic_phase<C, true, true>, k_sac_actor_phase<C, true, true, true>): a
+// tile's two critics are independent up to 32 q values, so the two waves of a pair (waves 2j and 2j + 1 of the
+// grid, both in one workgroup) take one critic each (the wave's role c) and the unit of work is half a tile.
+//   pair j = global wave >> 1, P = 2 gridDim pairs, iteration k = 0 .. K - 1 works on tile j + k P,
+//   K = ceil(ntiles / P): from kernel arguments only, so every wave of every workgroup runs K iterations and
+//   reaches the one barrier of each; a pair whose tile is past the end skips the work, not the barrier.
+// The q values cross through an LDS slot [pair in workgroup][k & 1][c][32]: written before the barrier, the
+// partner's read behind it; the next write to the same parity is two barriers later, behind the partner's read.
+struct PairMap {
+  int c, j, P, K;
+};
+__device__ __forceinline__ PairMap pair_map(int ntiles) {
+  const int gw = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWavesPerWG + (threadIdx.x >> 6)));
+  const int P = 2 * (int)gridDim.x;
+  return {gw & 1, gw >> 1, P, (ntiles + P - 1) / P};
+}
+using PairSlot = float[kWavesPerWG / 2][2][2][32];
+
+// The soft-min twin target y (sac_acm.py:50-56) of one sample: one expression for every form of the critic phase.
+__device__ __forceinline__ float sac_target_y(const SacArgs& p, int b, float q1t, float q2t, float alpha, float lp2) {
+  const float notdone = 1.f - p.DN[b];
+  return fadd_rn(p.R[b], fmul_rn(p.gamma * notdone, fsub_rn(fminf(q1t, q2t), alpha * lp2)));
+}
+
 // ============================================================================ critic phase
 // STAGED (the stage split): the target action comes from k_sac_trunk_fwd / k_sac_squash_stage; the kernel starts
 // at the target critics, from their action input (p.SCA) and log pi' (p.SLP).
-template <class C, bool STAGED = false>
+// PAIR (with STAGED): wave pairs, above.  Wave c runs target critic c, then critic c's forward and backward.  Its
+// two fc3 accumulator sets are the slabs of the unpaired kernel's waves j (even k) and j + P (odd k): with
+// W = 2 P waves, those walk tiles j, j + W, .. and j + P, j + P + W, .. in this order, so every slab holds the same
+// sums of the same tiles in the same order, and is written by one wave.
+template <class C, bool STAGED = false, bool PAIR = false>
 __global__ __launch_bounds__(256, 1) void k_sac_critic_phase(SacArgs p) {
+  static_assert(STAGED || !PAIR, "the pair form starts at the target critics");
+  static_assert(C::F3 || !PAIR, "the pair form keeps the fused fc3 slabs");
   __shared__ __attribute__((aligned(16))) float smem[kWavesPerWG * kLdsPerWave];
   __shared__ __attribute__((aligned(16))) float tbl[kTabMax];
   __shared__ __attribute__((aligned(16))) float s_dq[kWavesPerWG][32];  // the tile's d loss / dq, for the fused layer-3 weight gradient
@@ -589,14 +620,35 @@ __global__ __launch_bounds__(256, 1) void k_sac_critic_phase(SacArgs p) {
   const int ld = p.Bp;
   const float alpha = *p.alpha;
   float w3a[4] = {0.f, 0.f, 0.f, 0.f}, w3b[4] = {0.f, 0.f, 0.f, 0.f}, b3a = 0.f, b3b = 0.f;  // fused fc3 grads
-  for (int tile = blockIdx.x * kWavesPerWG + w; tile < ntiles; tile += gridDim.x * kWavesPerWG) {
+  const PairMap pm = PAIR ? pair_map(ntiles) : PairMap{};
+  int tile = PAIR ? pm.j : blockIdx.x * kWavesPerWG + w;
+  for (int k = 0; PAIR ? k < pm.K : tile < ntiles; ++k, tile += PAIR ? pm.P : gridDim.x * kWavesPerWG) {
     const Lane L = make_lane(big, small, tbl, ld, tile * 32 + (lane & 31));
     const int b = L.b;
     const bool valid = b < p.B;
     uint64_t d0 = 0, d1 = 0, d2 = 0, d3 = 0;
     float lp2;
     f32x16 tin[C::NB_CIN];
-    if constexpr (STAGED) {
+    float q1t, q2t;
+    if constexpr (PAIR) {
+      const bool active = tile < ntiles;  // wave-uniform, and the same for both waves of the pair
+      __shared__ PairSlot s_q;  // (here: only the pair forms hold it)
+      float* slot = &s_q[w >> 1][k & 1][0][0];
+      float qt = 0.f;
+      if (active) {
+        SPP_TP(0);
+        load_cat_gg<C::NB_OB, C::NB_CA>(tin, p.S2, C::OB, p.SCA, C::CA, L.ld4, L.vo);
+        lp2 = p.SLP[b];
+        SPP_TP(5);
+        qt = critic_forward<C, false, 6>(p.targ[pm.c], tin, L, nullptr, nullptr, d0, d1, d2, d3);
+        if (L.h == 0) slot[32 * pm.c + L.s] = qt;
+      }
+      __syncthreads();  // every wave of the workgroup, K times
+      if (!active) continue;
+      const float qo = slot[32 * (pm.c ^ 1) + L.s];
+      q1t = pm.c ? qo : qt;
+      q2t = pm.c ? qt : qo;
+    } else if constexpr (STAGED) {
       SPP_TP(0);
       load_cat_gg<C::NB_OB, C::NB_CA>(tin, p.S2, C::OB, p.SCA, C::CA, L.ld4, L.vo);
       lp2 = p.SLP[b];
@@ -621,15 +673,19 @@ __global__ __launch_bounds__(256, 1) void k_sac_critic_phase(SacArgs p) {
       }
     }
     // ---- soft-min twin target (:50-56)
-    SPP_TP(5);
-    const float q1t = critic_forward<C, false, 6>(p.targ[0], tin, L, nullptr, nullptr, d0, d1, d2, d3);
-    const float q2t = critic_forward<C, false, 8>(p.targ[1], tin, L, nullptr, nullptr, d0, d1, d2, d3);
-    const float notdone = 1.f - p.DN[b];
-    const float y = fadd_rn(p.R[b], fmul_rn(p.gamma * notdone, fsub_rn(fminf(q1t, q2t), alpha * lp2)));
-    // ---- both critics: forward, MSE grad, backward to weight-gradient operands (:117-131)
+    if constexpr (!PAIR) {
+      SPP_TP(5);
+      q1t = critic_forward<C, false, 6>(p.targ[0], tin, L, nullptr, nullptr, d0, d1, d2, d3);
+      q2t = critic_forward<C, false, 8>(p.targ[1], tin, L, nullptr, nullptr, d0, d1, d2, d3);
+    }
+    const float y = sac_target_y(p, b, q1t, q2t, alpha, lp2);
+    // ---- both critics (PAIR: this wave's): forward, MSE grad, backward to weight-gradient operands (:117-131)
     float lq0 = 0.f, lq1 = 0.f;
+    const int i0 = PAIR ? pm.c : 0, i1 = PAIR ? pm.c + 1 : 2;
 #pragma unroll 1
-    for (int i = 0; i < 2; ++i) {
+    for (int i = i0; i < i1; ++i) {
+      // the fc3 accumulator set: critic i's (PAIR: the slab of even / of odd iterations)
+      const bool seta = PAIR ? (k & 1) == 0 : i == 0;
       uint64_t m1lo = 0, m1hi = 0, m2lo = 0, m2hi = 0;
       f32x16 xin[C::NB_CIN];
       load_cat_gg<C::NB_OB, C::NB_CA>(xin, p.S, C::OB, C::ACMC ? p.AENV : p.ACT, C::CA, L.ld4, L.vo);
@@ -660,11 +716,11 @@ __global__ __launch_bounds__(256, 1) void k_sac_critic_phase(SacArgs p) {
           const int s2 = (j + u) & 31;
           acc = fmaf(row[s2], s_dq[w][s2], acc);
         }
-        if (i == 0) w3a[k] += acc;
+        if (seta) w3a[k] += acc;
         else w3b[k] += acc;
       }
       const float dsum = wave_sum(L.h == 0 ? dq : 0.f);
-      if (i == 0) b3a += dsum;
+      if (seta) b3a += dsum;
       else b3b += dsum;
       SPP_XLANE_SYNC();  // the image rows are rewritten by the delta2 staging below
       }
@@ -706,16 +762,17 @@ __global__ __launch_bounds__(256, 1) void k_sac_critic_phase(SacArgs p) {
     SPP_TP(14);
     const float s0 = wave_sum(lq0), s1 = wave_sum(lq1);
     if (lane == 0) {
-      p.part[tile * kParts + 0] = s0;
-      p.part[tile * kParts + 1] = s1;
+      if (!PAIR || pm.c == 0) p.part[tile * kParts + 0] = s0;
+      if (!PAIR || pm.c == 1) p.part[tile * kParts + 1] = s1;
     }
     SPP_TP(15);
   }
   // this wave's fc3 partials [256 weights | bias] per critic (every wave writes, tiles or not)
+  // PAIR: slabs j and j + P of this wave's critic
   if constexpr (C::F3) {
     const int64_t wg = (int64_t)blockIdx.x * kWavesPerWG + w;
-    float* o0 = p.W3P[0] + wg * p.w3p_stride;
-    float* o1 = p.W3P[1] + wg * p.w3p_stride;
+    float* o0 = PAIR ? p.W3P[pm.c] + (int64_t)pm.j * p.w3p_stride : p.W3P[0] + wg * p.w3p_stride;
+    float* o1 = PAIR ? p.W3P[pm.c] + (int64_t)(pm.j + pm.P) * p.w3p_stride : p.W3P[1] + wg * p.w3p_stride;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       o0[lane + 64 * k] = w3a[k];
@@ -966,9 +1023,12 @@ __device__ __forceinline__ void actor_trunk_backward(const SacArgs& p, const Lan
 // k_sac_actor_heads<C, true> (everything after it, in the original sample order).
 // STAGED (the stage split, with SPLIT): a, logpi and the critics' input come from k_sac_trunk_fwd /
 // k_sac_squash_stage (p.SCA, p.SLP; the trunk kernel has stored the trunk's masks); the kernel is the critics.
-template <class C, bool SPLIT = false, bool STAGED = false>
+// PAIR (with STAGED; wave pairs, above the critic phase): wave c runs critic c and stores its masks; behind the
+// exchange the role-0 wave does what one wave does for the tile: q = min, the partials, SEL and the counts.
+template <class C, bool SPLIT = false, bool STAGED = false, bool PAIR = false>
 __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratch z) {
   static_assert(SPLIT || !STAGED, "the stage split cuts the split phase");
+  static_assert(STAGED || !PAIR, "the pair form is the staged kernel's");
   __shared__ float smem[kWavesPerWG * kLdsPerWave];
   __shared__ __attribute__((aligned(16))) float tbl[kTabMax];
   SPP_TP_INIT();
@@ -979,7 +1039,9 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
   const int ntiles = p.Bp / 32;
   const int ld = p.Bp;
   const float alpha = *p.alpha;
-  for (int tile = blockIdx.x * kWavesPerWG + w; tile < ntiles; tile += gridDim.x * kWavesPerWG) {
+  const PairMap pm = PAIR ? pair_map(ntiles) : PairMap{};
+  int tile = PAIR ? pm.j : blockIdx.x * kWavesPerWG + w;
+  for (int k = 0; PAIR ? k < pm.K : tile < ntiles; ++k, tile += PAIR ? pm.P : gridDim.x * kWavesPerWG) {
     const Lane L = make_lane(big, small, tbl, ld, tile * 32 + (lane & 31));
     const int b = L.b;
     const bool valid = b < p.B;
@@ -990,7 +1052,26 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
     float lp;
     f32x16 cin[C::NB_CIN];
     constexpr bool kWide = C::NB_PAIR > 2;
-    if constexpr (STAGED) {
+    uint64_t ma0 = 0, ma1 = 0, ma2 = 0, ma3 = 0, mb0 = 0, mb1 = 0, mb2 = 0, mb3 = 0;
+    float q1, q2;
+    if constexpr (PAIR) {
+      const bool active = tile < ntiles;  // wave-uniform, and the same for both waves of the pair
+      __shared__ PairSlot s_q;  // (here: only the pair forms hold it)
+      float* slot = &s_q[w >> 1][k & 1][0][0];
+      if (active) {
+        SPP_TP(26);
+        load_cat_gg<C::NB_OB, C::NB_CA>(cin, p.S, C::OB, p.SCA, C::CA, L.ld4, L.vo);
+        q1 = critic_forward<C, false>(p.critic[pm.c], cin, L, nullptr, nullptr, ma0, ma1, ma2, ma3);
+        if (L.h == 0) slot[32 * pm.c + L.s] = q1;
+        uint4* cm = reinterpret_cast<uint4*>(z.CM + (((int64_t)pm.c * ld + b) * 2 + L.h) * 4);
+        cm[0] = make_uint4((uint32_t)ma0, (uint32_t)(ma0 >> 32), (uint32_t)ma1, (uint32_t)(ma1 >> 32));
+        cm[1] = make_uint4((uint32_t)ma2, (uint32_t)(ma2 >> 32), (uint32_t)ma3, (uint32_t)(ma3 >> 32));
+      }
+      __syncthreads();  // every wave of the workgroup, K times
+      if (!active || pm.c != 0) continue;
+      q2 = slot[32 + L.s];
+      lp = p.SLP[b];
+    } else if constexpr (STAGED) {
       SPP_TP(26);
       load_cat_gg<C::NB_OB, C::NB_CA>(cin, p.S, C::OB, p.SCA, C::CA, L.ld4, L.vo);
       lp = p.SLP[b];
@@ -1029,9 +1110,10 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
     }
     SPP_TP(29);  // ACM forward
     // ---- q = min(Q1, Q2)(s, c)  (:73-75), masks kept for the backward
-    uint64_t ma0 = 0, ma1 = 0, ma2 = 0, ma3 = 0, mb0 = 0, mb1 = 0, mb2 = 0, mb3 = 0;
-    const float q1 = critic_forward<C, false>(p.critic[0], cin, L, nullptr, nullptr, ma0, ma1, ma2, ma3);
-    const float q2 = critic_forward<C, false>(p.critic[1], cin, L, nullptr, nullptr, mb0, mb1, mb2, mb3);
+    if constexpr (!PAIR) {
+      q1 = critic_forward<C, false>(p.critic[0], cin, L, nullptr, nullptr, ma0, ma1, ma2, ma3);
+      q2 = critic_forward<C, false>(p.critic[1], cin, L, nullptr, nullptr, mb0, mb1, mb2, mb3);
+    }
     const float qmin = fminf(q1, q2);
     // torch.minimum backward: ties split the gradient in half
     const float gq = valid ? -p.inv_B : 0.f;
@@ -1043,12 +1125,14 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_phase(SacArgs p, AcmScratc
       // tile's list counts, the trunk's masks and the loss partials that need logpi / qmin.
       const int sel = valid ? (int)(q1 <= q2) | ((int)(q2 <= q1) << 1) : 0;
       if (L.h == 0) z.SEL[b] = (uint8_t)sel;
-      uint4* cm0 = reinterpret_cast<uint4*>(z.CM + ((int64_t)b * 2 + L.h) * 4);
-      uint4* cm1 = reinterpret_cast<uint4*>(z.CM + (((int64_t)ld + b) * 2 + L.h) * 4);
-      cm0[0] = make_uint4((uint32_t)ma0, (uint32_t)(ma0 >> 32), (uint32_t)ma1, (uint32_t)(ma1 >> 32));
-      cm0[1] = make_uint4((uint32_t)ma2, (uint32_t)(ma2 >> 32), (uint32_t)ma3, (uint32_t)(ma3 >> 32));
-      cm1[0] = make_uint4((uint32_t)mb0, (uint32_t)(mb0 >> 32), (uint32_t)mb1, (uint32_t)(mb1 >> 32));
-      cm1[1] = make_uint4((uint32_t)mb2, (uint32_t)(mb2 >> 32), (uint32_t)mb3, (uint32_t)(mb3 >> 32));
+      if constexpr (!PAIR) {  // (PAIR: each wave has stored its critic's)
+        uint4* cm0 = reinterpret_cast<uint4*>(z.CM + ((int64_t)b * 2 + L.h) * 4);
+        uint4* cm1 = reinterpret_cast<uint4*>(z.CM + (((int64_t)ld + b) * 2 + L.h) * 4);
+        cm0[0] = make_uint4((uint32_t)ma0, (uint32_t)(ma0 >> 32), (uint32_t)ma1, (uint32_t)(ma1 >> 32));
+        cm0[1] = make_uint4((uint32_t)ma2, (uint32_t)(ma2 >> 32), (uint32_t)ma3, (uint32_t)(ma3 >> 32));
+        cm1[0] = make_uint4((uint32_t)mb0, (uint32_t)(mb0 >> 32), (uint32_t)mb1, (uint32_t)(mb1 >> 32));
+        cm1[1] = make_uint4((uint32_t)mb2, (uint32_t)(mb2 >> 32), (uint32_t)mb3, (uint32_t)(mb3 >> 32));
+      }
       const int n1 = __popcll(__ballot(L.h == 0 && (sel & 1))), n2 = __popcll(__ballot(L.h == 0 && (sel & 2)));
       if constexpr (!STAGED) {
         uint64_t* mk = z.MASK + (int64_t)tile * 4 * 64 + lane;
