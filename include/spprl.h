@@ -370,6 +370,11 @@ sppStatus sppAgentStageSplit(sppAgentHandle h, int* bits_out);
  * under SPP_CRITIC_PAIRS=0 (read at creation; the default is 1, and 3 asks for both).  The small-batch team
  * kernels are not paired. */
 sppStatus sppAgentCriticPairs(sppAgentHandle h, int* bits_out);
+/* Waves per workgroup of the kernel that runs this handle's fp32 256 x 256 weight-gradient items (batches of 8,192
+ * padded samples and more): 8 (k_dw_big8, two waves per SIMD) or 4 (k_dw_big), as SPP_DW_BIG_WAVES asked when the
+ * agent was created (the default is 8); always 4 for mlp_bf16 handles, whose items run in the 4-wave k_dw_big16.
+ * The results of the two forms are identical bit for bit. */
+sppStatus sppAgentDwBigWaves(sppAgentHandle h, int* waves_out);
 sppStatus sppAgentGetTiming(sppAgentHandle h, double* ms_out /*[5]*/, int64_t* count_out /*[5]*/);
 
 /* Rollout action (rltoolkit/acm/off_policy/ddpg_acm.py:40-50 noise_action +

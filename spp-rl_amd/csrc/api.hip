@@ -1181,7 +1181,7 @@ void launch_dw_set(DwSet& D, int ph, hipStream_t st) {
   const int* ij = D.items.ptr + D.ioff[ph];
   const int* is = ij + D.nitems[ph];
   const DwJob* jobs = D.jobs.ptr + D.j0[ph];
-  launch_dw_kernels(jobs, ij, is, D.nitems[ph], D.nlds[ph], D.nj[ph], D.max_elems[ph], D.bf16, st);
+  launch_dw_kernels(jobs, ij, is, D.nitems[ph], D.nlds[ph], D.nj[ph], D.max_elems[ph], D.bf16, D.big_waves, st);
 }
 
 // polls before a k_mlp_sgd arrival wait times out (0: the kernel's default); test hook sppSetSgdSpinLimit
@@ -1244,6 +1244,7 @@ constexpr int kStageWGPerCU = 3;
 constexpr int kStageSplitAll = 7;
 constexpr int kStageSplitDefault = kStageSplitAll;
 constexpr int kCriticPairsDefault = 1;  // bit 1 measured inside the run-to-run range: off unless asked for
+constexpr int kDwBigWavesDefault = 8;
 static int stage_grid(sppAgent* a, int Bp) {
   return std::max(1, std::min(cdiv(Bp / 32, kWavesPerWG), kStageWGPerCU * a->num_cu));
 }
@@ -1374,6 +1375,11 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
     const int wantp = cp ? atoi(cp) : kCriticPairsDefault;
     if ((a->stage_split & 4) && ks.critic_rest_pair) a->critic_pairs |= wantp & 1;
     if ((a->stage_split & 2) && ks.critics_a_pair) a->critic_pairs |= wantp & 2;
+    // waves of the fp32 256 x 256 weight-gradient kernel (dw.hip): 8 = k_dw_big8, 4 = k_dw_big; the bf16 sets'
+    // k_dw_big16 has 4
+    const char* bw = getenv("SPP_DW_BIG_WAVES");
+    const int wantw = bw ? atoi(bw) : kDwBigWavesDefault;
+    for (DwSet& D : a->dws) D.big_waves = wantw == 8 && !cfg->mlp_bf16 ? 8 : 4;
   }
   const int ob = cfg->ob, aout = cfg->aout, ac = cfg->ac;
   a->cin = ob + (cfg->acm_critic ? ac : aout);
@@ -1686,6 +1692,12 @@ sppStatus sppAgentStageSplit(sppAgentHandle a, int* bits_out) {
 sppStatus sppAgentCriticPairs(sppAgentHandle a, int* bits_out) {
   SPP_REQUIRE(a && bits_out, SPP_E_INVALID_ARG, "null");
   *bits_out = a->critic_pairs;
+  return SPP_OK;
+}
+
+sppStatus sppAgentDwBigWaves(sppAgentHandle a, int* waves_out) {
+  SPP_REQUIRE(a && waves_out, SPP_E_INVALID_ARG, "null");
+  *waves_out = a->dws[0].big_waves;
   return SPP_OK;
 }
 

@@ -152,6 +152,12 @@ __device__ __forceinline__ void dw_tile(const float* const (&ap)[4], const float
 // (row r at 128 r bytes); the 16-B slot q of row r holds piece q ^ ((r >> 1) & 7) of the row (the
 // swizzle is applied on the global SOURCE address and undone on the read), which makes the MFMA
 // operand reads (lane c reads row c of its block, ds_read_b128) bank-conflict free.
+// SPP_DW_TIMING (tools/build_variant.py only; the results are WRONG on purpose, the variants are timed, never shipped
+// or tested): bit 0 drops the per-step DMA issue of k_dw_big and k_dw_big8 after the first two steps, bit 1 their
+// per-step wait and barrier.  What each costs the two loops: DESIGN.md §8, round 15.
+#ifndef SPP_DW_TIMING
+#define SPP_DW_TIMING 0
+#endif
 typedef __attribute__((address_space(1))) void glob_void;
 typedef __attribute__((address_space(3))) void lds_void;
 __device__ __forceinline__ void dw_big_lds(const DwJob& J, int b_begin, int nsteps, int nb0, int kb0, bool db,
@@ -234,12 +240,117 @@ __device__ __forceinline__ void dw_big_lds(const DwJob& J, int b_begin, int nste
     rd(lds[t & 1], 1, ra1, rx1);
     mm(ra0, rx0);
     if (t + 1 < nsteps) {
+#if !(SPP_DW_TIMING & 2)
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // my DMA for t + 1 landed, my reads of t done
       __syncthreads();  // every wave's DMA landed and every wave is done reading buffer t & 1
+#endif
+#if !(SPP_DW_TIMING & 1)
       if (t + 2 < nsteps) issue(t + 2, t & 1);
+#endif
       rd(lds[(t + 1) & 1], 0, ra0, rx0);
     }
     mm(ra1, rx1);
+  }
+}
+
+// dw_big_lds for a workgroup of 8 waves, two on each SIMD (k_dw_big8): while one wave of a SIMD issues DMA, reads LDS
+// or waits at the step's barrier, its partner's MFMAs keep the matrix pipe busy.  The LDS image, the swizzle, the two
+// buffers and the barrier per step are dw_big_lds's; per wave:
+//   output   4 row blocks x 2 column blocks (128 accumulator registers): waves w and w + 4, which share a SIMD, hold the
+//            two column halves of dw_big_lds's quadrant w, so every 32 x 32 block sees the same MFMA chain in the same
+//            order and the bias sums come from the waves with column blocks 0-1 by the same expression
+//   DMA      8 of the step's 64 instructions: rows 64 w .. 64 w + 63 of [A | X]
+//   reads    12 ds_read_b128 per sub-step (4 A rows, 2 X rows, two 16-B slots each), as two quarter-steps of 6
+// The two waves of a SIMD are kept out of phase by where they issue the DMA for step t + 2 behind step t's barrier:
+// waves 0-3 at once (their partners run the step's last 32 MFMAs meanwhile), waves 4-7 after those MFMAs (beside
+// their partners').  Either way the DMA follows the barrier that ends every wave's reads of the buffer, and is waited for
+// before the next one.  Every barrier's trip count comes from nsteps alone.
+__device__ __forceinline__ void dw_big8_lds(const DwJob& J, int b_begin, int nsteps, int nb0, int kb0, bool db,
+                                            f32x16 (&acc)[4][2], float (&bs)[4]) {
+  __shared__ __attribute__((aligned(16))) float lds[2][512 * 32];
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, h = lane >> 5, c = lane & 31;
+  const int64_t ld = J.Bp;
+  // instruction k of wave w: rows 64 w + 8 k + (lane >> 3), slot lane & 7 <- piece (lane & 7) ^ ((row >> 1) & 7)
+  //   = (lane & 7) ^ ((lane >> 4) & 3) ^ (4 (k & 1))
+  const int pe = (lane & 7) ^ ((lane >> 4) & 3);
+  const int wu = __builtin_amdgcn_readfirstlane(w);
+  const float* wsel = wu < 4 ? J.A : J.X0;
+  const uint64_t wbits = (uint64_t)(size_t)wsel;
+  const uint64_t wbu = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wbits) |
+                       ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wbits >> 32)) << 32);
+  const int64_t ldu = (int64_t)__builtin_amdgcn_readfirstlane((int)ld);  // Bp < 2^31
+  const int bbu = __builtin_amdgcn_readfirstlane(b_begin);
+  const float* wb = opaque(reinterpret_cast<const float*>((size_t)wbu) + (int64_t)(64 * (wu & 3)) * ldu + bbu);
+  const uint32_t off0 = (uint32_t)((lane >> 3) * ld + 4 * pe), off1 = off0 ^ 16u;  // pe ^ 4: 16 floats
+  const bool late = wu >= 4;  // the SIMD's second wave
+  auto issue = [&](int t, int buf) {
+    const uint32_t dst = (uint32_t)(size_t)(lds_void*)&lds[buf][(64 * wu) * 32];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float* src = opaque(wb + ((int64_t)(8 * k) * ldu + 32 * t)) + ((k & 1) ? off1 : off0);
+      uint32_t keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep)
+                   : "v"(src), "s"(dst + 1024u * k)
+                   : "memory");
+    }
+  };
+  // A step is read in 4 quarter-steps of 8 samples per lane half: quarter v = one 16-B slot per row, piece
+  // 4 (v >> 1) + 2 h + (v & 1) of the row, which is the order in which dw_big_lds's sub-steps (two slots each) feed
+  // them to the MFMAs.  The operand registers are double-buffered across quarter-steps: the 6 reads of the next are
+  // in flight under the current one's 32 MFMAs.
+  const int sw = (c >> 1) & 7;  // the read-side swizzle of rows 32 b + c
+  auto rd = [&](const float* L, int v, float4 (&ra)[4], float4 (&rx)[2]) {
+    const int q = (4 * (v >> 1) + 2 * h + (v & 1)) ^ sw;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ra[i] = *reinterpret_cast<const float4*>(L + (32 * (nb0 + i) + c) * 32 + 4 * q);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) rx[j] = *reinterpret_cast<const float4*>(L + (256 + 32 * (kb0 + j) + c) * 32 + 4 * q);
+  };
+  auto mm = [&](const float4 (&ra)[4], const float4 (&rx)[2]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float4 av = ra[i];
+      if (db) bs[i] += (av.x + av.y) + (av.z + av.w);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const float4 xv = rx[j];
+        acc[i][j] = mfma(av.x, xv.x, acc[i][j]);
+        acc[i][j] = mfma(av.y, xv.y, acc[i][j]);
+        acc[i][j] = mfma(av.z, xv.z, acc[i][j]);
+        acc[i][j] = mfma(av.w, xv.w, acc[i][j]);
+      }
+    }
+  };
+  issue(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (nsteps > 1) issue(1, 1);
+  float4 ra0[4], rx0[2], ra1[4], rx1[2];
+  rd(lds[0], 0, ra0, rx0);
+#pragma unroll 1
+  for (int t = 0; t < nsteps; ++t) {
+    const float* L = lds[t & 1];
+    rd(L, 1, ra1, rx1);
+    mm(ra0, rx0);
+    rd(L, 2, ra0, rx0);
+    mm(ra1, rx1);
+    rd(L, 3, ra1, rx1);
+    mm(ra0, rx0);
+    if (t + 1 < nsteps) {
+#if !(SPP_DW_TIMING & 2)
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // my DMA for t + 1 landed, my reads of t done
+      __syncthreads();  // every wave's DMA landed and every wave is done reading buffer t & 1
+#endif
+#if !(SPP_DW_TIMING & 1)
+      if (!late && t + 2 < nsteps) issue(t + 2, t & 1);
+#endif
+      rd(lds[(t + 1) & 1], 0, ra0, rx0);
+    }
+    mm(ra1, rx1);
+#if !(SPP_DW_TIMING & 1)
+    if (late && t + 2 < nsteps) issue(t + 2, t & 1);  // behind step t's barrier: t + 2 < nsteps implies it ran
+#endif
   }
 }
 
@@ -321,8 +432,10 @@ __device__ __forceinline__ void dw_big_lds16(const DwJob& J, int b_begin, int ns
 
 // Partial (or final) result of an item's (nb0, kb0) quadrant; rows >= nrow2 go to the second output
 // (dW2 / db2).
+// NJ: column blocks the wave holds (k_dw_big8: 2).
+template <int NJ = 4>
 __device__ __forceinline__ void dw_store(const DwJob& J, int split, int part, int nb0, int kb0, int ni, int nj,
-                                         bool db, const f32x16 (&acc)[4][4], const float (&bs)[4]) {
+                                         bool db, const f32x16 (&acc)[4][NJ], const float (&bs)[4]) {
   // recomputed here, not carried over the tile loop: the prologue's per-row indices, kept live across the
   // MFMA loop for these stores, were what spilled to scratch
   int tid = threadIdx.x;
@@ -347,7 +460,7 @@ __device__ __forceinline__ void dw_store(const DwJob& J, int split, int part, in
       float* rowp = row_w(n);
       asm volatile("" : "+v"(rowp));  // keep the row pointer from being hoisted across the unrolled rows
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < NJ; ++j) {
         if (j >= nj) break;
         const int k = 32 * (kb0 + j) + c;
         if (k < K) rowp[k] = acc[i][j][q];
@@ -565,6 +678,34 @@ __global__ void k_dw_reduce(const DwJob* __restrict__ jobs) {
     if (n < J.nrow2) J.db[n] = s;
     else J.db2[n - J.nrow2] = s;
   }
+}
+
+// k_dw_big's items on 8 waves, two per SIMD (dw_big8_lds; at most 256 registers per wave): wave w holds column blocks
+// 2 (w >> 2) .. + 1 of k_dw_big's quadrant w & 3.  Same items, slabs and results as k_dw_big, bit for bit.
+// A template (of nothing) that the launch function names after k_dw<>, so that it is emitted behind every other kernel
+// of the unit and those keep the place in the code object that they had without it.
+constexpr int kDwBig8Threads = 512;
+template <int = 0>
+__global__ __launch_bounds__(kDwBig8Threads, 1) void k_dw_big8(const DwJob* __restrict__ jobs,
+                                                               const int* __restrict__ item_job,
+                                                               const int* __restrict__ item_split) {
+  const int item = blockIdx.x;
+  const DwJob J = jobs[item_job[item]];
+  const int split = item_split[item];
+  const int w = threadIdx.x >> 6;
+  const int nb0 = 4 * ((w >> 1) & 1), kb0 = 4 * (w & 1) + 2 * (w >> 2);
+  const int b_begin = split * J.split_len;
+  const int b_end = min(b_begin + J.split_len, J.Bp);
+  const int nsteps = (b_end - b_begin) / 32;  // ranges are multiples of 32 samples
+  const bool db = J.db != nullptr && kb0 == 0;
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = zero16();
+  float bs[4] = {0.f, 0.f, 0.f, 0.f};
+  if (nsteps > 0) dw_big8_lds(J, b_begin, nsteps, nb0, kb0, db, acc, bs);
+  dw_store<2>(J, split, 0, nb0, kb0, 4, 2, db, acc, bs);
 }
 
 }  // namespace spp

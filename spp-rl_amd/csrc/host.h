@@ -45,6 +45,7 @@ struct DwSet {
   int nlds[2] = {0, 0};  // leading items of a phase that run as k_dw_big / k_dw_big16 (256 x 256 jobs)
   int64_t max_elems[2] = {1, 1};  // reduce lanes per phase: largest [N*K | N] image x its dw_red_group
   bool bf16 = false;              // bf16 MFMA job set (k_dw<true>)
+  int big_waves = 4;              // waves of the fp32 256 x 256 items' kernel: 4 k_dw_big, 8 k_dw_big8 (SPP_DW_BIG_WAVES)
   void release() { slab.release(); jobs.release(); items.release(); }
 };
 

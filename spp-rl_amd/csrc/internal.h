@@ -27,9 +27,10 @@ struct DwJob {
 // dw.hip (own translation unit, ks_dw.hip): the split-K weight-gradient launch + fixed-order reduce
 // over nitems work items of jobs[0, njobs); item_job / item_split index the job table; the first
 // nlds items are 256 x 256 jobs staged through LDS (k_dw_big; bf16 sets: k_dw_big16, bf16 A and X rows), the
-// rest run in k_dw; bf16: the set's jobs are bf16 MFMA jobs (DwJob::bf16).
+// rest run in k_dw; bf16: the set's jobs are bf16 MFMA jobs (DwJob::bf16); big_waves: 8 runs the fp32 256 x 256
+// items as k_dw_big8 (two waves per SIMD), anything else as k_dw_big (bf16 sets: always k_dw_big16).
 void launch_dw_kernels(const DwJob* jobs, const int* item_job, const int* item_split, int nitems, int nlds,
-                       int njobs, int64_t max_elems, bool bf16, hipStream_t st);
+                       int njobs, int64_t max_elems, bool bf16, int big_waves, hipStream_t st);
 // k_dw_reduce: lanes that sum one output element of a job with nslab partial slabs of `elems` elements
 // (fixed-order reduce).  One lane per element (consecutive lanes read consecutive elements of a slab:
 // coalesced) for the split-K GEMM jobs; a group of 16 lanes per element for the few-element, many-slab jobs
