@@ -564,6 +564,33 @@ sppStatus sppOnpObsStats(const float* start_obs, int64_t n_start, const float* n
 sppStatus sppDebugDense(const float* x, const float* W, const float* b, float* y, int B, int K, int N, int act,
                         void* stream);
 
+/* Debug / kernel check: one phase of weight-gradient jobs through the agents' own planner (split assignment, item
+ * table, slab arena), launch function and kernels (csrc/dw.hip), then a stream synchronise:
+ *   dW [N][K0 + K1] = A [N][Bp] x [X0 | X1]^T,   db [N] = sum_b A,   rows >= nrow2 going to (dW2, db2).
+ * Operands are feature-major device arrays [rows][Bp], Bp = B rounded up to 32, 16-byte aligned, of fp32 or (bf16
+ * jobs with a_bf / x_bf set) bf16 elements.  The kernels sum over all Bp columns.  The contract of the columns
+ * B .. Bp - 1 is the per-sample kernels': A (a layer's output gradient) is ZERO there, because every loss gradient
+ * is masked by b < B; X (a layer's input) holds whatever the forward pass computed for an all-zero input row,
+ * finite but not zero.  Callers fill A's dead columns with zeros; the kernels may rely on nothing about X's.
+ * num_cu stands in for the device's compute-unit count in the planner (it sets the samples per work item);
+ * big_waves is 4 or 8 (k_dw_big / k_dw_big8 for the fp32 256 x 256 jobs at Bp >= 8192).  All jobs of a call have the
+ * same bf16 flag; N and K0 + K1 are at most 256; nrow2 is in [1, N] (N: one output, dW2 / db2 unused); db may be NULL
+ * (then db2 is unused too).  A fused job has no work items: the caller passes nsplit >= 2 partial slabs
+ * [nsplit][slab_stride], slab_stride = (N (K0 + K1) + N) rounded up to 4, each a [N (K0 + K1) | N] image, which are
+ * copied into the arena after planning and reduced in slab order (A, X0, X1 unused).  The arena is filled with NaN
+ * before the launch, so a slab element that is summed without having been written shows in the result.
+ * On return split_len and wsplit of every job, and nsplit of the jobs that are not fused, hold the plan. */
+typedef struct sppDwJobDesc {
+  const void *A, *X0, *X1;
+  float *dW, *db, *dW2, *db2;
+  const float* slabs; /* fused jobs only */
+  int N, K0, K1, nrow2;
+  int bf16, a_bf, x_bf, fused;
+  int nsplit;            /* in: fused jobs; out: the others */
+  int split_len, wsplit; /* out */
+} sppDwJobDesc;
+sppStatus sppDebugDwSet(sppDwJobDesc* jobs, int njobs, int B, int num_cu, int big_waves, void* stream);
+
 /* Profiling builds only (-DSPP_PROF): per-region s_memtime totals of the phase kernels. */
 sppStatus sppDebugReadProf(unsigned long long* out64 /*[64]*/, int reset);
 

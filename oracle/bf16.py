@@ -16,7 +16,7 @@ Where the kernels convert (spp-rl_amd/csrc; "R(.)" = one RNE fp32 -> bf16, every
   the two-tile critic phase (sac_bf.h, acm_critic sets) keeps the hand-off between layers as the bf16 operand
     itself: img16_put sac_bf.h:51-60 = R(fp32 epilogue value), the value dense16_lds_impl's reader would
     have converted; to_steps sac_bf.h:196-201 for register inputs.  Same roundings, same places.  That kernel
-    is an A/B variant: it is compiled only with -DSPP_BF16_TWO_TILES=1 (common.h:12-19, kset.h:36-38; default 0),
+    is an A/B variant: it is compiled only with -DSPP_BF16_TWO_TILES=1 (common.h:14-21, kset.h:36-38; default 0),
     so the library the tests load runs the one-tile k_sac_critic_phase (sac.hip) for every bf16 set.
   weight-gradient operands: op_st<C::BF> (mlp.h:614-618 -> fm_st16 mlp.h:608-612, R(v)) stores H1, H2, D1,
     D2, AH1, AH2, AD1, AD2 as bf16; k_dw reads those as they are (as_bf8 dw.hip:55,120) and converts the
@@ -42,7 +42,7 @@ Where the kernels convert (spp-rl_amd/csrc; "R(.)" = one RNE fp32 -> bf16, every
                                            sac.hip:382,388, sac_bf.h:361,365,423,434
                                                                                     R(DQ) R(H2)^T, db = sum DQ      api.hip critic_dw
                                                                                     (bf16 sets build with SPP_BF16_FUSE3 = 0:
-                                                                                    fc3 is a k_dw job, not fused, common.h:20)
+                                                                                    fc3 is a k_dw job, not fused, common.h:22)
   critic delta2 = dq w3 relu'(h2)          fp32 product        sac.hip:547,674, sac_bf.h:454
   critic W2^T . delta2                     R(D2) R(W2)         sac.hip:555,677, sac_bf.h:463  (D1 = relu' . acc, op_st sac.hip:558)
   critic W1a^T . delta1 (actor phase)      R(D1) R(W1)         sac.hip:682

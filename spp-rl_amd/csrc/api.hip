@@ -933,102 +933,25 @@ static void launch_pack(sppAgent* a, int first, int last, hipStream_t st) {
   if (n > 0) hipLaunchKernelGGL(k_pack_matrix, dim3(64, n), dim3(256), 0, st, (const PackJob*)(a->d_pj.ptr + off));
 }
 
-// bf16 sets' 256 x 256 bf16-operand weight gradients on the LDS-staged k_dw_big16 (0: k_dw<true>, the A/B)
-#ifndef SPP_DW_BIG16
-#define SPP_DW_BIG16 1
-#endif
 // ---- shared with api_onp.hip (host.h)
 namespace spp {
 
-// Split assignment, slab arena, item table and upload of a job set.
+// Split assignment, slab arena, item table (plan_dw, dw_plan.h) and upload of a job set.
 sppStatus finalize_dw(DwSet& D, std::vector<DwJob>& jobs, int nph, int Bp, int B, int num_cu) {
-  // Sample splits: the large (>= 128x128 padded) GEMMs of a phase share ~one
-  // workgroup per CU in proportion to their MACs; the small, HBM-bound ones
-  // take 2048-sample items.
-  auto is_big = [](const DwJob& j) {
-    return (int64_t)round_up(j.N, 32) * round_up(j.K0 + j.K1, 32) >= 128 * 128;
-  };
-  // 256 x 256 fp32 jobs run as their own launch (k_dw_big); the other large jobs share k_dw's launch
-  // (small batches -- vanilla SAC's B = 100, PPO minibatches -- keep one launch: k_dw's register tiles)
-  // (bf16 sets: the 256 x 256 jobs whose A and X rows are both bf16 run as k_dw_big16, in 64-sample steps)
-  auto lds_big = [Bp](const DwJob& j) {
-    return Bp >= 8192 && j.N == 256 && j.K0 == 256 && j.K1 == 0 &&
-           (!j.bf16 || (SPP_DW_BIG16 && j.a_bf && j.x_bf && Bp % 64 == 0));
-  };
-  auto assign_splits = [&](int first, int count) {
-    double big[2] = {0.0, 0.0};  // MACs of the large jobs per launch
-    for (int i = first; i < first + count; ++i)
-      if (!jobs[i].fused && is_big(jobs[i]))
-        big[lds_big(jobs[i]) ? 0 : 1] += (double)round_up(jobs[i].N, 32) * round_up(jobs[i].K0 + jobs[i].K1, 32);
-    for (int i = first; i < first + count; ++i) {
-      DwJob& j = jobs[i];
-      if (j.fused) continue;  // nsplit = the phase kernel's waves, set by the caller
-      const double pm = (double)round_up(j.N, 32) * round_up(j.K0 + j.K1, 32);
-      // outputs that fit one 128x128 wave quadrant: the 4 waves split each item's samples
-      const bool thin_n = j.N <= 128, thin_k = j.K0 + j.K1 <= 128;
-      j.wsplit = thin_n && thin_k ? 4 : (thin_n != thin_k ? 2 : 1);
-      // large jobs: ~one workgroup per CU over their launch, in proportion to their MACs; small jobs:
-      // >= 2048 samples per item, and at most ~256 slabs (the fixed-order reduce is serial over slabs)
-      int ns = is_big(j) ? (int)std::lround(num_cu * pm / big[lds_big(j) ? 0 : 1])
-                         : std::min(cdiv(Bp, 2048), std::max(1, 256 / j.wsplit));
-      // small batches (PPO minibatches of 512): at least 4 items, so each wave of an item takes one
-      // 32-sample unit instead of a serial chain over the whole batch
-      if (!is_big(j)) ns = std::max(ns, std::min(cdiv(Bp, 32 * j.wsplit), 4));
-      ns = std::max(1, std::min(ns, std::max(1, Bp / 32)));
-      j.split_len = (int)round_up(cdiv(Bp, ns), lds_big(j) && j.bf16 ? 64 : 32 * j.wsplit);
-      j.nsplit = cdiv(Bp, j.split_len);
-    }
-  };
-  for (int ph = 0; ph < nph; ++ph) assign_splits(D.j0[ph], D.nj[ph]);
-  // slabs: phases run back to back on one stream -> they share one arena
-  size_t need = 0;
-  for (int ph = 0; ph < nph; ++ph) {
-    size_t off = 0;
-    for (int j = D.j0[ph]; j < D.j0[ph] + D.nj[ph]; ++j) {
-      if (jobs[j].nsplit * jobs[j].wsplit > 1) {
-        jobs[j].slab = nullptr;
-        off += (size_t)jobs[j].nsplit * jobs[j].wsplit * jobs[j].slab_stride;
-      }
-    }
-    need = std::max(need, off);
-  }
-  if (need > D.slab.n) {
+  const DwPlan P = plan_dw(jobs, D.j0, D.nj, nph, Bp, num_cu);
+  if (P.need > D.slab.n) {
     D.slab.release();
-    SPP_CHECK_HIP(D.slab.alloc(need));
+    SPP_CHECK_HIP(D.slab.alloc(P.need));
   }
-  std::vector<int> items;
+  for (size_t j = 0; j < jobs.size(); ++j)
+    if (P.slab_off[j] >= 0) jobs[j].slab = D.slab.ptr + P.slab_off[j];
   for (int ph = 0; ph < nph; ++ph) {
-    size_t off = 0;
-    std::vector<int> jj, ss;
-    for (int j = D.j0[ph]; j < D.j0[ph] + D.nj[ph]; ++j) {
-      if (jobs[j].nsplit * jobs[j].wsplit > 1) {
-        jobs[j].slab = D.slab.ptr + off;
-        off += (size_t)jobs[j].nsplit * jobs[j].wsplit * jobs[j].slab_stride;
-      }
-    }
-    // large-GEMM items first (they set the phase's critical path): the 256 x 256 fp32 jobs (k_dw_big,
-    // LDS-DMA operands), then the other large ones, then the thin ones (k_dw)
-    D.nlds[ph] = 0;
-    for (int pass = 0; pass < 3; ++pass)
-      for (int j = D.j0[ph]; j < D.j0[ph] + D.nj[ph]; ++j) {
-        const int cls = lds_big(jobs[j]) ? 0 : (is_big(jobs[j]) ? 1 : 2);
-        if (cls != pass || jobs[j].fused) continue;
-        for (int sp = 0; sp < jobs[j].nsplit; ++sp) {
-          jj.push_back(j - D.j0[ph]);
-          ss.push_back(sp);
-          if (pass == 0) ++D.nlds[ph];
-        }
-      }
-    D.max_elems[ph] = 1;
-    for (int j = D.j0[ph]; j < D.j0[ph] + D.nj[ph]; ++j) {
-      const int64_t el = (int64_t)jobs[j].N * (jobs[j].K0 + jobs[j].K1) + jobs[j].N;
-      D.max_elems[ph] = std::max<int64_t>(D.max_elems[ph], el * dw_red_group(jobs[j].nsplit * jobs[j].wsplit, el));
-    }
-    D.ioff[ph] = (int)items.size();
-    D.nitems[ph] = (int)jj.size();
-    items.insert(items.end(), jj.begin(), jj.end());
-    items.insert(items.end(), ss.begin(), ss.end());
+    D.nlds[ph] = P.nlds[ph];
+    D.max_elems[ph] = P.max_elems[ph];
+    D.ioff[ph] = P.ioff[ph];
+    D.nitems[ph] = P.nitems[ph];
   }
+  const std::vector<int>& items = P.items;
   D.jobs.release();
   D.items.release();
   SPP_CHECK_HIP(D.jobs.alloc(jobs.size()));
@@ -2195,6 +2118,65 @@ sppStatus sppDebugDense(const float* x, const float* W, const float* b, float* y
   SPP_CHECK_HIP(hipGetLastError());
   SPP_CHECK_HIP(hipStreamSynchronize(st));
   hipFree(wf); hipFree(dj);
+  return SPP_OK;
+}
+
+// One phase of weight-gradient jobs through dw_job, finalize_dw and launch_dw_set: what the agents run (spprl.h).
+sppStatus sppDebugDwSet(sppDwJobDesc* descs, int njobs, int B, int num_cu, int big_waves, void* stream) {
+  SPP_REQUIRE(descs && njobs > 0 && njobs <= 64 && B > 0 && B <= (1 << 30) && num_cu > 0 && num_cu <= 4096 &&
+                  (big_waves == 4 || big_waves == 8),
+              SPP_E_INVALID_ARG, "debug dw: njobs %d B %d num_cu %d big_waves %d", njobs, B, num_cu, big_waves);
+  const int Bp = (int)round_up(B, 32);
+  auto al16 = [](const void* p) { return ((size_t)p & 15) == 0; };
+  std::vector<DwJob> jobs;
+  for (int i = 0; i < njobs; ++i) {
+    const sppDwJobDesc& d = descs[i];
+    SPP_REQUIRE(d.N > 0 && d.N <= 256 && d.K0 > 0 && d.K1 >= 0 && d.K0 + d.K1 <= 256, SPP_E_INVALID_ARG,
+                "debug dw: job %d N %d K0 %d K1 %d", i, d.N, d.K0, d.K1);
+    SPP_REQUIRE(d.nrow2 >= 1 && d.nrow2 <= d.N && d.dW && (d.nrow2 == d.N || (d.dW2 && (!d.db || d.db2))),
+                SPP_E_INVALID_ARG, "debug dw: job %d nrow2 %d of %d rows, or an output is null", i, d.nrow2, d.N);
+    SPP_REQUIRE((d.bf16 != 0) == (descs[0].bf16 != 0) && (d.bf16 || (!d.a_bf && !d.x_bf)), SPP_E_INVALID_ARG,
+                "debug dw: job %d bf16 %d a_bf %d x_bf %d (job 0: bf16 %d)", i, d.bf16, d.a_bf, d.x_bf, descs[0].bf16);
+    if (d.fused)
+      SPP_REQUIRE(d.nsplit >= 2 && d.nsplit <= (1 << 20) && d.slabs, SPP_E_INVALID_ARG,
+                  "debug dw: fused job %d nsplit %d, or slabs null", i, d.nsplit);
+    else
+      SPP_REQUIRE(d.A && d.X0 && (d.K1 == 0 || d.X1) && al16(d.A) && al16(d.X0) && al16(d.X1), SPP_E_INVALID_ARG,
+                  "debug dw: job %d operand null or not 16-byte aligned", i);
+    DwJob& j = dw_job(jobs, Bp, (const float*)d.A, d.N, (const float*)d.X0, d.K0, (const float*)d.X1, d.K1, d.dW, d.db,
+                      d.nrow2, d.dW2, d.db2);
+    j.bf16 = d.bf16 ? 1 : 0;
+    j.a_bf = d.a_bf ? 1 : 0;
+    j.x_bf = d.x_bf ? 1 : 0;
+    if (d.fused) {
+      j.fused = 1;
+      j.nsplit = d.nsplit;
+      j.wsplit = 1;
+    }
+  }
+  hipStream_t st = S(stream);
+  DwSet D;
+  struct Release {
+    DwSet& D;
+    ~Release() { D.release(); }
+  } release{D};
+  D.j0[0] = 0;
+  D.nj[0] = njobs;
+  D.big_waves = big_waves;
+  const sppStatus s = finalize_dw(D, jobs, 1, Bp, B, num_cu);
+  if (s) return s;
+  if (D.slab.n) SPP_CHECK_HIP(hipMemsetAsync(D.slab.ptr, 0xff, sizeof(float) * D.slab.n, st));  // NaN
+  for (int i = 0; i < njobs; ++i) {
+    descs[i].split_len = jobs[i].split_len;
+    descs[i].wsplit = jobs[i].wsplit;
+    if (!jobs[i].fused) descs[i].nsplit = jobs[i].nsplit;
+    else
+      SPP_CHECK_HIP(hipMemcpyAsync(jobs[i].slab, descs[i].slabs, sizeof(float) * jobs[i].nsplit * jobs[i].slab_stride,
+                                   hipMemcpyDeviceToDevice, st));
+  }
+  launch_dw_set(D, 0, st);
+  SPP_CHECK_HIP(hipGetLastError());
+  SPP_CHECK_HIP(hipStreamSynchronize(st));
   return SPP_OK;
 }
 

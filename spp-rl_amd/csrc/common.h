@@ -5,6 +5,8 @@
 
 #include <string>
 
+#include "intmath.h"  // round_up, cdiv
+
 // bf16 SAC kernel sets: fuse the critics' fc3 weight gradient into the critic phase (1) or hand h2 / dq to a
 // k_dw job (0).  Compile-time A/B (tools/build_variant.py -DSPP_BF16_FUSE3=...); fp32 sets always fuse.
 // Measured round 5 (Ant bf16, 100 steps, profiles/r05/ab_fuse3_*.json): fused critic phase 1.8145 ms,
@@ -60,9 +62,6 @@ const char* get_error();
       return code;                          \
     }                                       \
   } while (0)
-
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-inline int cdiv(int64_t x, int64_t m) { return (int)((x + m - 1) / m); }
 
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

@@ -52,6 +52,14 @@ class ReplayView(ctypes.Structure):
                 ("rec_acm", c_int), ("rec_act", c_int)]
 
 
+class DwJobDesc(ctypes.Structure):
+    """sppDwJobDesc (spprl.h): one weight-gradient job of sppDebugDwSet."""
+    _fields_ = [("A", c_void_p), ("X0", c_void_p), ("X1", c_void_p), ("dW", c_void_p), ("db", c_void_p),
+                ("dW2", c_void_p), ("db2", c_void_p), ("slabs", c_void_p), ("N", c_int), ("K0", c_int), ("K1", c_int),
+                ("nrow2", c_int), ("bf16", c_int), ("a_bf", c_int), ("x_bf", c_int), ("fused", c_int),
+                ("nsplit", c_int), ("split_len", c_int), ("wsplit", c_int)]
+
+
 P = ctypes.POINTER
 # name: (restype, argtypes)
 _SIGS = {
@@ -183,6 +191,7 @@ _SIGS = {
     "sppAcmSgdWorkgroups": (c_int, [c_void_p, c_int]),
     "sppDebugReadProf": (c_int, [c_void_p, c_int]),
     "sppDebugDense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "sppDebugDwSet": (c_int, [P(DwJobDesc), c_int, c_int, c_int, c_int, c_void_p]),  # jobs, njobs, B, num_cu, big_waves
 }
 EXPORTED = tuple(_SIGS)
 
