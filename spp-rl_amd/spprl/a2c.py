@@ -20,26 +20,11 @@ import torch
 
 from . import config
 from ._lib import call, ptr, stream_handle
-from .ppo_vanilla import _ACM_ONLY, PPO
+from .ppo_vanilla import PPO
 
-PPO_ONLY = ("epsilon", "ppo_epsilon", "gae_lambda", "kl_div_threshold", "max_ppo_epochs", "ppo_batch_size",
-            "entropy_coef")
 # PPO.__init__'s loop / environment keywords A2C passes through
 _LOOP_KWARGS = ("iterations", "stats_freq", "test_episodes", "return_done", "max_frames", "n_envs", "env", "env_spec",
                 "device", "seed", "loop_seed")
-
-
-def refuse_keywords(owner, kw, acm=True):
-    """TypeError for PPO's keywords (A2C.__init__, a2c.py:17-27, takes none of them) and, for the vanilla class, the
-    AcM's: raised before the library is touched."""
-    bad = sorted(k for k in kw if k in PPO_ONLY)
-    if bad:
-        raise TypeError("%s got unexpected keyword argument(s): %s (PPO options: use PPO%s)"
-                        % (owner, ", ".join(bad), "" if acm else "_AcM"))
-    bad = sorted(k for k in kw if k.startswith("acm_") or k in _ACM_ONLY) if acm else []
-    if bad:
-        raise TypeError("%s got unexpected keyword argument(s): %s (SPP / AcM options: use A2C_AcM)"
-                        % (owner, ", ".join(bad)))
 
 
 def refuse_process_group(owner):
@@ -53,7 +38,7 @@ class A2C(PPO):
     def __init__(self, env_name="HalfCheetah-v2", gamma=config.GAMMA, actor_lr=3e-3, critic_lr=3e-4,
                  critic_num_target_updates=10, num_critic_updates_per_target=10, normalize_adv=True,
                  obs_norm_alpha=0.99, batch_size=config.BATCH_SIZE, **kw):
-        refuse_keywords("A2C", kw)
+        config.refuse_keywords("A2C", kw, config.ACM_ONLY_ON_POLICY, config.PPO_ONLY)
         config.check_kwargs("A2C", {k: v for k, v in kw.items() if k not in _LOOP_KWARGS},
                             {k: v for k, v in config.ON_POLICY_NO_EFFECT_KWARGS.items() if k != "obs_norm_alpha"})
         refuse_process_group("A2C")

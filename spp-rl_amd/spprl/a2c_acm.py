@@ -19,14 +19,14 @@ Out of scope: data parallelism (single process), discrete actions.
 import torch
 
 from . import config
-from .a2c import refuse_keywords, refuse_process_group
+from .a2c import refuse_process_group
 from .ppo_acm import PPO_AcM
 
 
 class A2C_AcM(PPO_AcM):
     def __init__(self, env_name="HalfCheetah-v2", gamma=config.GAMMA, actor_lr=3e-3, critic_lr=3e-4,
                  batch_size=config.BATCH_SIZE, custom_loss=0.0, **kw):
-        refuse_keywords("A2C_AcM", kw, acm=False)
+        config.refuse_keywords("A2C_AcM", kw, ppo_only=config.PPO_ONLY)
         refuse_process_group("A2C_AcM")
         for k in ("rehearse_world", "dp_update", "comm"):  # PPO_AcM's data-parallel options
             if kw.get(k) is not None:

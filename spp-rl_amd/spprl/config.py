@@ -76,6 +76,30 @@ def check_kwargs(owner, kw, allowed=None):
                         % (owner, ", ".join(bad), ", ".join(sorted(allowed))))
 
 
+# Keywords of the reference's other constructor chains, refused by name (refuse_keywords):
+#   the AcMTrainer / AcMOffPolicy / DDPG_AcM options the vanilla off-policy classes do not take
+#   (SAC -> DDPG -> RL -> MetaLearner, sac.py:17-25, ddpg.py:19-33, rl.py:17-26),
+ACM_ONLY_OFF_POLICY = ("custom_loss", "norm_closs", "denormalize_actor_out", "unbiased_update", "acm_critic")
+#   the AcMOnPolicyTrainer options the vanilla on-policy classes do not take (ppo.py:15-25, a2c.py:17-27),
+ACM_ONLY_ON_POLICY = ("custom_loss", "norm_closs", "denormalize_actor_out", "min_max_denormalize")
+#   and PPO's own, which A2C.__init__ (a2c.py:17-27) does not take
+PPO_ONLY = ("epsilon", "ppo_epsilon", "gae_lambda", "kl_div_threshold", "max_ppo_epochs", "ppo_batch_size",
+            "entropy_coef")
+
+
+def refuse_keywords(owner, kw, acm_only=None, ppo_only=()):
+    """TypeError, as the reference's constructor chain raises it, for the keywords of another class: ``ppo_only``
+    names, and for a vanilla class (``acm_only`` given) every ``acm_*`` keyword and the ``acm_only`` names.  The
+    message points at the class that takes them.  Called first in a constructor: before the library is touched."""
+    bad = sorted(k for k in kw if k in ppo_only)
+    hint = "PPO options: use PPO" + ("_AcM" if owner.endswith("_AcM") else "")
+    if not bad and acm_only is not None:
+        bad = sorted(k for k in kw if k.startswith("acm_") or k in acm_only)
+        hint = "SPP / AcM options: use %s_AcM" % owner
+    if bad:
+        raise TypeError("%s got unexpected keyword argument(s): %s (%s)" % (owner, ", ".join(bad), hint))
+
+
 def default_max_batch(update_batch_size, kw):
     """Largest batch the agent's device scratch must hold when the caller gives no
     ``max_batch``: the reference batch, or with E > 1 envs the fused schedule's rho*E

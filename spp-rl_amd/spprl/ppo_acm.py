@@ -28,7 +28,7 @@ batch_size frames, as the reference does.
 import numpy as np
 import torch
 
-from . import config
+from . import _lib, config
 from ._lib import call, ptr, stream_handle
 from .onpolicy import OnPolicyNets
 from .ppo import calculate_gae
@@ -516,13 +516,9 @@ class PPO_AcM:
         from .onpolicy import actor_layout, critic_layout
         from . import nets as _nets
 
-        rb = self.replay_buffer
         return {"actor": _nets.state_dict(self.nets.params[0], actor_layout(self.ob_dim, self.ob_dim)),
                 "critic": _nets.state_dict(self.nets.params[1], critic_layout(self.ob_dim)),
-                "obs_mean": rb.obs_mean.cpu(), "obs_std": rb.obs_std.cpu(),
-                "min_obs": rb.min_obs.cpu() if rb._have_minmax else None,
-                "max_obs": rb.max_obs.cpu() if rb._have_minmax else None,
-                "acm": self.acm.net_state(5)}
+                **self.replay_buffer.normalizer_state(), "acm": self.acm.net_state(_lib.SPP_NET_ACM)}
 
     def apply_params_dict(self, d):  # rl.py:263-279 + ACM (acm/on_policy.py)
         from .onpolicy import actor_layout, critic_layout
@@ -531,10 +527,8 @@ class PPO_AcM:
         for i, (k, lay) in enumerate((("actor", actor_layout(self.ob_dim, self.ob_dim)),
                                       ("critic", critic_layout(self.ob_dim)))):
             _nets.load_state(self.nets.params[i], lay, d[k])
-        self.acm.apply_params_dict({"actor": self.acm.net_state(0), "critic_1": self.acm.net_state(1),
-                                    "critic_2": self.acm.net_state(2), "acm": d["acm"], "obs_mean": d["obs_mean"],
-                                    "obs_std": d["obs_std"], "min_obs": d.get("min_obs"),
-                                    "max_obs": d.get("max_obs")})
+        self.acm.load_net(_lib.SPP_NET_ACM, d["acm"])
+        self.replay_buffer.load_normalizer_state(d)
 
     def save(self, path):  # rl.py:281-292
         from .checkpoint import save_params

@@ -35,8 +35,6 @@ from .onpolicy import OnPolicyNets, actor_layout, critic_layout, obs_stats
 from .ppo import calculate_gae
 from .trainer import StatsLogger, SynthVecEnv
 
-_ACM_ONLY = ("custom_loss", "norm_closs", "denormalize_actor_out", "min_max_denormalize")
-
 
 class PPO:
     def __init__(self, env_name="HalfCheetah-v2", gamma=config.GAMMA, actor_lr=3e-3, critic_lr=3e-4, epsilon=0.2,
@@ -47,10 +45,7 @@ class PPO:
                  env=None, env_spec=None, device="cuda", seed=None, loop_seed=0, **unused):
         # PPO -> A2C -> RL -> MetaLearner (ppo.py:15-25, a2c.py:17-27, rl.py:116-132, 17-26) take no AcM keyword and
         # no **kwargs at the end of the chain: raised here, before the library is touched
-        acm_only = sorted(k for k in unused if k.startswith("acm_") or k in _ACM_ONLY)
-        if acm_only:
-            raise TypeError("PPO got unexpected keyword argument(s): %s (SPP / AcM options: use PPO_AcM)"
-                            % ", ".join(acm_only))
+        config.refuse_keywords("PPO", unused, config.ACM_ONLY_ON_POLICY)
         config.check_kwargs("PPO", unused, {k: v for k, v in config.ON_POLICY_NO_EFFECT_KWARGS.items()
                                             if k != "obs_norm_alpha"})  # (taken explicitly and honoured)
         import torch.distributed as dist

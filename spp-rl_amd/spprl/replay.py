@@ -349,6 +349,22 @@ class BufferAcMOffPolicy:
             step += 1
         self._have_minmax = True
 
+    def normalizer_state(self):
+        """The normaliser's four checkpoint entries (rl.py:267-270), in the reference's key order; the min-max pair
+        is None until a statistics update (or a load) has set it."""
+        return {"obs_mean": self.obs_mean.cpu(), "obs_std": self.obs_std.cpu(),
+                "min_obs": self.min_obs.cpu() if self._have_minmax else None,
+                "max_obs": self.max_obs.cpu() if self._have_minmax else None}
+
+    def load_normalizer_state(self, d):
+        """rl.py:276-279: mean and std always; the min-max pair only when the checkpoint holds both."""
+        self.obs_mean.copy_(torch.as_tensor(d["obs_mean"]))
+        self.obs_std.copy_(torch.as_tensor(d["obs_std"]))
+        if d.get("min_obs") is not None and d.get("max_obs") is not None:
+            self.min_obs.copy_(torch.as_tensor(d["min_obs"]))
+            self.max_obs.copy_(torch.as_tensor(d["max_obs"]))
+            self._have_minmax = True
+
     def normalize(self, obs, force=False):
         """BufferAcMOffPolicy.normalize (replay_buffer.py:77-81) -> MemoryMeta.normalize (memory.py:76-88)."""
         if not (self.obs_norm or force):

@@ -299,8 +299,16 @@ class HostSynthEnv(HostVecEnv):
 
 
 class OffPolicyLoop:
-    """Trainer mixin of SAC_AcM / DDPG_AcM.  The host class provides ``act``,
-    ``update``, ``replay_buffer``, ``bucket_acm``, ``_h`` and ``_fused_update(idx, ctr, allreduce, beside)``."""
+    """The training loop of the off-policy agents (offpolicy.OffPolicyAgent).  The host class provides ``act``,
+    ``update``, ``replay_buffer``, ``bucket_acm``, ``_h`` and ``_fused_update(idx, ctr, allreduce, beside)`` (with
+    VANILLA also ``update_from_replay(idx, seed, ctr)``), sets ``env_name``, ``ob_dim``, ``ac_dim``,
+    ``actor_output_dim``, ``device``, ``update_batch_size``, ``acm_lr`` and ``acm_critic`` before ``_init_loop``, and
+    overrides the switches below where it differs."""
+    VANILLA = False  # the reference's plain algorithm: plain ReplayBuffer, env-sampled initial actions, staged updates
+    acm_kind = "acm"  # "acm": the AcM net sppAcmSgd covers; "basic": BasicAcM; None: no ACM
+    unbiased_update = False  # make_unbiased_update (ddpg_acm.py:59-73)
+    max_ep_len = None  # Q3: set only where a time-limit end is not done (rl.py:185); AcMOffPolicy keeps None
+    env_spec = None  # (ob, ac, action high, episode limit) when given instead of a config.ENV_SPECS name
 
     def _init_loop(self, iterations=config.ITERATIONS, batch_size=config.BATCH_SIZE, stats_freq=config.STATS_FREQ,
                    test_episodes=None, return_done=None, max_frames=None, random_frames=config.RANDOM_FRAMES,
@@ -335,7 +343,7 @@ class OffPolicyLoop:
             self.tensorboard_writer = TensorboardWriter(tensorboard_dir)
         ob, ac = self.ob_dim, self.ac_dim
         if env is None:
-            spec = getattr(self, "env_spec", None) or config.ENV_SPECS.get(self.env_name, (ob, ac, 1.0, 1000))
+            spec = self.env_spec or config.ENV_SPECS.get(self.env_name, (ob, ac, 1.0, 1000))
             env = SynthVecEnv(n_envs, ob, ac, max_episode_steps=spec[3], ac_high=spec[2], seed=loop_seed,
                               device=self.device)
         self.env = env
@@ -490,7 +498,7 @@ class OffPolicyLoop:
         E = self.n_envs
         rb = self.replay_buffer
         mode = 0 if self.stats_logger.frames < self.random_frames else 1  # initial_act (off_policy.py:50-54)
-        vanilla = getattr(self, "VANILLA", False)
+        vanilla = self.VANILLA
         if mode == 0 and vanilla:
             self.env.sample_actions(self._eps)  # DDPG.initial_act: env.action_space.sample() (ddpg.py:178-180)
         else:
@@ -513,7 +521,7 @@ class OffPolicyLoop:
         # done = end, except at the time limit when max_ep_len is set (Q3, ddpg.py:210-212);
         # AcMOffPolicy keeps max_ep_len None (off_policy.py:43)
         done_dev = end_dev
-        max_ep = getattr(self, "max_ep_len", None)
+        max_ep = self.max_ep_len
         if max_ep is not None:
             self._ep_len += 1
             if any_end:
@@ -547,12 +555,12 @@ class OffPolicyLoop:
         """Reference cadence (ddpg.py:231-237, ddpg_acm.py:75-85), one frame at a time.  unbiased_update
         (make_unbiased_update, ddpg_acm.py:59-73): the sampled next obs is the critic's action."""
         if self.update_condition():
-            unbiased = getattr(self, "unbiased_update", False)
+            unbiased = self.unbiased_update
             rb = self.replay_buffer
             # vanilla SAC on the device: the same MT19937 index draw as sample_batch (replay_buffer.py:234), staged
             # feature-major straight from the ring (one gather kernel instead of a row-major gather + restage) with
             # the rsample noise drawn on the device
-            staged = getattr(self, "VANILLA", False) and self.device.type == "cuda"
+            staged = self.VANILLA and self.device.type == "cuda"
             for _ in range(self.grad_steps):
                 if staged:
                     idx = np.random.randint(0, len(rb), self.update_batch_size)
@@ -610,7 +618,7 @@ class OffPolicyLoop:
         norm = bool(rb.obs_norm) and not (rb.min_max_denormalize and not rb._have_minmax)  # normalize() no-ops
         if norm and not rb.HAS_ACM:  # the plain ReplayBuffer (vanilla SAC): z-score (zeros / ones before any stats)
             norm = 2
-        unbiased = bool(getattr(self, "unbiased_update", False)) and not self.acm_critic  # acm_critic: acm_action
+        unbiased = bool(self.unbiased_update) and not self.acm_critic  # acm_critic: acm_action
         if norm or unbiased:
             call("sppAgentStagePost", self._h, int(norm), int(unbiased), st)
 
@@ -678,7 +686,7 @@ class OffPolicyLoop:
     def _acm_sgd_ok(self, bs):
         """The persistent one-launch SGD kernel (sppAcmSgd) covers the AcM of these dims, one rank, and
         batches whose workgroups are all co-resident on this device (sppAcmSgdMaxBatch)."""
-        if not (getattr(self, "acm_kind", "acm") == "acm" and self.allreduce is None
+        if not (self.acm_kind == "acm" and self.allreduce is None
                 and (self.ob_dim, self.ac_dim) in ((11, 3), (17, 6), (3, 1))):
             return False
         if getattr(self, "_sgd_max_bs", None) is None:
