@@ -375,6 +375,12 @@ sppStatus sppAgentCriticPairs(sppAgentHandle h, int* bits_out);
  * agent was created (the default is 8); always 4 for mlp_bf16 handles, whose items run in the 4-wave k_dw_big16.
  * The results of the two forms are identical bit for bit. */
 sppStatus sppAgentDwBigWaves(sppAgentHandle h, int* waves_out);
+/* Work items of this handle's current weight-gradient job sets (as of its last updates) that run in k_dw_thin, the
+ * LDS-staged kernel of the thin fp32 jobs (one side of the gradient a single 32-block: the first layers' and the
+ * heads'); 0: none, every such item runs in k_dw.  The kernel takes them from SPP_DW_THIN_MIN_BP padded samples on
+ * (default 8192; the variable exists so that tests reach one-step items) unless SPP_DW_THIN=0, both read when the
+ * agent is created; never for mlp_bf16 handles.  The results of the two routings are identical bit for bit. */
+sppStatus sppAgentDwThin(sppAgentHandle h, int* items_out);
 sppStatus sppAgentGetTiming(sppAgentHandle h, double* ms_out /*[5]*/, int64_t* count_out /*[5]*/);
 
 /* Rollout action (rltoolkit/acm/off_policy/ddpg_acm.py:40-50 noise_action +
@@ -579,7 +585,10 @@ sppStatus sppDebugDense(const float* x, const float* W, const float* b, float* y
  * [nsplit][slab_stride], slab_stride = (N (K0 + K1) + N) rounded up to 4, each a [N (K0 + K1) | N] image, which are
  * copied into the arena after planning and reduced in slab order (A, X0, X1 unused).  The arena is filled with NaN
  * before the launch, so a slab element that is summed without having been written shows in the result.
- * On return split_len and wsplit of every job, and nsplit of the jobs that are not fused, hold the plan. */
+ * The thin fp32 jobs run as k_dw_thin from SPP_DW_THIN_MIN_BP padded samples on (default 8192; SPP_DW_THIN=0: never),
+ * both read at the call.
+ * On return split_len and wsplit of every job, and nsplit of the jobs that are not fused, hold the plan, and thin
+ * tells which jobs' items k_dw_thin ran. */
 typedef struct sppDwJobDesc {
   const void *A, *X0, *X1;
   float *dW, *db, *dW2, *db2;
@@ -588,6 +597,7 @@ typedef struct sppDwJobDesc {
   int bf16, a_bf, x_bf, fused;
   int nsplit;            /* in: fused jobs; out: the others */
   int split_len, wsplit; /* out */
+  int thin;              /* out: 1 when the job's items ran in k_dw_thin (SPP_DW_THIN, SPP_DW_THIN_MIN_BP) */
 } sppDwJobDesc;
 sppStatus sppDebugDwSet(sppDwJobDesc* jobs, int njobs, int B, int num_cu, int big_waves, void* stream);
 

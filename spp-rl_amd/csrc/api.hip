@@ -938,7 +938,7 @@ namespace spp {
 
 // Split assignment, slab arena, item table (plan_dw, dw_plan.h) and upload of a job set.
 sppStatus finalize_dw(DwSet& D, std::vector<DwJob>& jobs, int nph, int Bp, int B, int num_cu) {
-  const DwPlan P = plan_dw(jobs, D.j0, D.nj, nph, Bp, num_cu);
+  const DwPlan P = plan_dw(jobs, D.j0, D.nj, nph, Bp, num_cu, D.thin_min_bp);
   if (P.need > D.slab.n) {
     D.slab.release();
     SPP_CHECK_HIP(D.slab.alloc(P.need));
@@ -947,6 +947,7 @@ sppStatus finalize_dw(DwSet& D, std::vector<DwJob>& jobs, int nph, int Bp, int B
     if (P.slab_off[j] >= 0) jobs[j].slab = D.slab.ptr + P.slab_off[j];
   for (int ph = 0; ph < nph; ++ph) {
     D.nlds[ph] = P.nlds[ph];
+    D.nthin[ph] = P.nthin[ph];
     D.max_elems[ph] = P.max_elems[ph];
     D.ioff[ph] = P.ioff[ph];
     D.nitems[ph] = P.nitems[ph];
@@ -1104,7 +1105,8 @@ void launch_dw_set(DwSet& D, int ph, hipStream_t st) {
   const int* ij = D.items.ptr + D.ioff[ph];
   const int* is = ij + D.nitems[ph];
   const DwJob* jobs = D.jobs.ptr + D.j0[ph];
-  launch_dw_kernels(jobs, ij, is, D.nitems[ph], D.nlds[ph], D.nj[ph], D.max_elems[ph], D.bf16, D.big_waves, st);
+  launch_dw_kernels(jobs, ij, is, D.nitems[ph], D.nlds[ph], D.nthin[ph], D.nj[ph], D.max_elems[ph], D.bf16,
+                    D.big_waves, st);
 }
 
 // polls before a k_mlp_sgd arrival wait times out (0: the kernel's default); test hook sppSetSgdSpinLimit
@@ -1168,6 +1170,17 @@ constexpr int kStageSplitAll = 7;
 constexpr int kStageSplitDefault = kStageSplitAll;
 constexpr int kCriticPairsDefault = 1;  // bit 1 measured inside the run-to-run range: off unless asked for
 constexpr int kDwBigWavesDefault = 8;
+// The padded batch from which a job set's thin fp32 weight gradients run as k_dw_thin (dw.hip), 0: never.
+// SPP_DW_THIN=0 turns the kernel off (every such item then runs in k_dw, as before it existed; the results are the
+// same bit for bit; the default is on: DESIGN.md §8, round 16).  SPP_DW_THIN_MIN_BP moves the threshold (default 8192, the LDS kernels' boundary): it exists for
+// the tests, which reach parts of one or no step with it.  Read when a job set's owner is made.
+static int dw_thin_min_bp() {
+  const char* t = getenv("SPP_DW_THIN");
+  if (t && atoi(t) == 0) return 0;
+  const char* m = getenv("SPP_DW_THIN_MIN_BP");
+  const int v = m ? atoi(m) : 8192;
+  return v >= 32 ? v : 32;
+}
 static int stage_grid(sppAgent* a, int Bp) {
   return std::max(1, std::min(cdiv(Bp / 32, kWavesPerWG), kStageWGPerCU * a->num_cu));
 }
@@ -1303,6 +1316,7 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
     const char* bw = getenv("SPP_DW_BIG_WAVES");
     const int wantw = bw ? atoi(bw) : kDwBigWavesDefault;
     for (DwSet& D : a->dws) D.big_waves = wantw == 8 && !cfg->mlp_bf16 ? 8 : 4;
+    for (DwSet& D : a->dws) D.thin_min_bp = dw_thin_min_bp();
   }
   const int ob = cfg->ob, aout = cfg->aout, ac = cfg->ac;
   a->cin = ob + (cfg->acm_critic ? ac : aout);
@@ -1621,6 +1635,14 @@ sppStatus sppAgentCriticPairs(sppAgentHandle a, int* bits_out) {
 sppStatus sppAgentDwBigWaves(sppAgentHandle a, int* waves_out) {
   SPP_REQUIRE(a && waves_out, SPP_E_INVALID_ARG, "null");
   *waves_out = a->dws[0].big_waves;
+  return SPP_OK;
+}
+
+sppStatus sppAgentDwThin(sppAgentHandle a, int* items_out) {
+  SPP_REQUIRE(a && items_out, SPP_E_INVALID_ARG, "null");
+  *items_out = 0;
+  for (const DwSet& D : a->dws)
+    if (D.B >= 0) *items_out += D.nthin[0] + D.nthin[1];
   return SPP_OK;
 }
 
@@ -2163,8 +2185,15 @@ sppStatus sppDebugDwSet(sppDwJobDesc* descs, int njobs, int B, int num_cu, int b
   D.j0[0] = 0;
   D.nj[0] = njobs;
   D.big_waves = big_waves;
+  D.thin_min_bp = dw_thin_min_bp();
   const sppStatus s = finalize_dw(D, jobs, 1, Bp, B, num_cu);
   if (s) return s;
+  {  // which jobs' items run in k_dw_thin: the table's last nthin items
+    std::vector<int> it(D.nitems[0]);  // item_job
+    SPP_CHECK_HIP(hipMemcpy(it.data(), D.items.ptr + D.ioff[0], sizeof(int) * it.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < njobs; ++i) descs[i].thin = 0;
+    for (int k = D.nitems[0] - D.nthin[0]; k < D.nitems[0]; ++k) descs[it[k]].thin = 1;
+  }
   if (D.slab.n) SPP_CHECK_HIP(hipMemsetAsync(D.slab.ptr, 0xff, sizeof(float) * D.slab.n, st));  // NaN
   for (int i = 0; i < njobs; ++i) {
     descs[i].split_len = jobs[i].split_len;

@@ -708,4 +708,223 @@ __global__ __launch_bounds__(kDwBig8Threads, 1) void k_dw_big8(const DwJob* __re
   dw_store<2>(J, split, 0, nb0, kb0, 4, 2, db, acc, bs);
 }
 
+// Thin fp32 jobs (host: plan_dw's thin_ok -- wsplit == 2 with one side a single 32-block: the first-layer weight
+// gradients D1 x [s | a]^T, AD1 x s^T and the head rows x h2^T), listed last in a phase's item table: HBM-bound items
+// whose operand rows k_dw streams 16 B per row and instruction.  Here the rows arrive by LDS-DMA as whole 128-B lines, 8
+// rows per wave-instruction (dw_big_lds's image: lane-linear, row R of a part at 128 R bytes, its 16-B slot q holding
+// piece q ^ ((R >> 1) & 7)).  Two forms, the same slabs bit for bit:
+//   split (the default)   a workgroup of 4 waves owns ONE sample part of an item (blockIdx = 2 item + part), 72 KiB of
+//            LDS, so a CU holds two workgroups whose barriers are independent: one's MFMAs run under the other's LDS
+//            reads, waits and barriers.  Measured: 0.173 ms per Hopper launch against
+//            0.212 ms for the joint form, whose two waves per SIMD meet at the same barriers.
+//   joint (-DSPP_DW_THIN_SPLIT=0, tools/build_variant.py)   a workgroup of 8 waves owns both parts of an item, 144 KiB.
+//   LDS      [2 buffers][parts][288 rows][128 B]: rows 0..255 the wide side's (A when N > 128, else [X0 | X1]), rows
+//            256..287 the narrow side's; only groups of 8 rows that hold a live row are fetched, and a lane of such a
+//            group past the last live row fetches that last row again (its LDS row is never read)
+//   DMA      wave w fetches the wide rows of its own blocks, and one narrow group of 8 rows
+//   MFMA     wave w holds block(s) 8 / kDwThinWaves * w .. of the wide side x the narrow block, one accumulator per
+//            part: per 32-sample step a chain of 16 v_mfma_f32_32x32x2_f32 per (block, part), in dw_tile's order
+//            (16-sample step t, P = 0, 1, e = 0..3: lane half h feeds sample 16 t + 8 h + 4 P + e), so every 32 x 32
+//            block of every slab holds what k_dw<false> writes, bit for bit; bias sums by dw_tile's expression in the
+//            same order, from the waves with column block 0; stores through dw_store
+//   step t   ds_read the step's operands into registers | lgkmcnt(0), barrier: buffer t & 1 is free | DMA of step
+//            t + 2 into it | the step's MFMAs | vmcnt(what step t + 2 issued): this wave's rows of step t + 1 landed
+//            (issued a whole step earlier), barrier: every wave's did.  Two steps are in flight beside the one in
+//            registers.
+// Every barrier's trip count comes from the workgroup's own step count alone: the split form's is its part's (an empty
+// part, the ragged last item's, runs no step and stores its all-zero slab); the joint form's is part 0's, which is never
+// the shorter one, and a shorter or empty part 1 skips its DMA, reads and MFMAs and reaches every barrier.
+#ifndef SPP_DW_THIN_SPLIT
+#define SPP_DW_THIN_SPLIT 1
+#endif
+#ifndef SPP_DW_THIN_WAVES
+#define SPP_DW_THIN_WAVES (SPP_DW_THIN_SPLIT ? 4 : 8)
+#endif
+// SPP_DW_THIN_TIMING (tools/build_variant.py only, as SPP_DW_TIMING: bits 0 and 1 give WRONG results on purpose, the
+// variants are timed, never shipped or tested): bit 0 drops the DMA issue after the first two steps, bit 1 replaces a
+// step's MFMAs by one multiply-add per operand word, bit 2 marks the DMA loads nt.
+#ifndef SPP_DW_THIN_TIMING
+#define SPP_DW_THIN_TIMING 0
+#endif
+constexpr int kDwThinWaves = SPP_DW_THIN_WAVES;
+constexpr int kDwThinThreads = 64 * kDwThinWaves;
+constexpr int kDwThinRows = 288;
+constexpr bool kDwThinSplit = SPP_DW_THIN_SPLIT != 0;  // a workgroup per (item, part), two workgroups per CU
+static_assert(kDwThinWaves == 4 || kDwThinWaves == 8, "k_dw_thin: 4 or 8 waves");
+template <int = 0>
+__global__ __launch_bounds__(kDwThinThreads, kDwThinSplit ? 2 : 1) void k_dw_thin(const DwJob* __restrict__ jobs,
+                                                               const int* __restrict__ item_job,
+                                                               const int* __restrict__ item_split) {
+  __shared__ __attribute__((aligned(16))) float lds[2][kDwThinSplit ? 1 : 2][kDwThinRows * 32];
+  constexpr int NW = kDwThinWaves, BPW = 8 / NW, WG = 32 / NW;  // blocks and 8-row DMA groups of the wide side per wave
+  const int item = kDwThinSplit ? blockIdx.x >> 1 : blockIdx.x;
+  const int mypart = kDwThinSplit ? blockIdx.x & 1 : 0;
+  const DwJob J = jobs[item_job[item]];
+  const int split = item_split[item];
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, c = lane & 31;
+  const int wu = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int N = J.N, K = J.K0 + J.K1;
+  const bool wideA = N > 128;  // k_dw's wsplit == 2 rule: the waves spread along the side that is wider than 128
+  const int nwide = wideA ? N : K, nnar = wideA ? K : N;
+  // the two parts' sample ranges, as k_dw's (whole 32-sample units)
+  const int i_begin = split * J.split_len;
+  const int s_end = min(i_begin + J.split_len, J.Bp);
+  const int q = (((s_end - i_begin + 1) / 2) + 31) & ~31;
+  const int b1 = min(i_begin + q, s_end);
+  const int m0 = (b1 - i_begin) / 32, m1 = (min(b1 + q, s_end) - b1) / 32;  // m1 <= m0; m1 > 0: b1 = i_begin + q
+  // split form: this workgroup's part runs as "part 0" below, and there is no part 1
+  const int s_begin = mypart ? b1 : i_begin;
+  const int n0 = __builtin_amdgcn_readfirstlane(mypart ? m1 : m0);
+  const int n1 = __builtin_amdgcn_readfirstlane(kDwThinSplit ? 0 : m1);
+  const int64_t ld = J.Bp;
+  auto rowp = [&](bool a_side, int r) -> const float* {
+    if (a_side) return J.A + (int64_t)r * ld;
+    return r < J.K0 ? J.X0 + (int64_t)r * ld : J.X1 + (int64_t)(r - J.K0) * ld;
+  };
+  // DMA sources at part 0's first sample: lane l of a group fetches piece (l & 7) ^ ((R >> 1) & 7) of LDS row
+  // R = 8 g + (l >> 3)
+  const float* srcw[WG];
+  int cw = 0;  // this wave's live wide groups
+#pragma unroll
+  for (int k = 0; k < WG; ++k) {
+    const int R = 8 * (WG * wu + k) + (lane >> 3);
+    srcw[k] = rowp(wideA, min(R, nwide - 1)) + s_begin + 4 * ((lane & 7) ^ ((R >> 1) & 7));
+    cw += 8 * (WG * wu + k) < nwide;
+  }
+  const int gn = wu & 3;  // narrow group; 8 waves: of part wu >> 2, 4 waves: of both parts
+  const int Rn = 8 * gn + (lane >> 3);
+  const float* srcn = rowp(!wideA, min(Rn, nnar - 1)) + s_begin + 4 * ((lane & 7) ^ ((Rn >> 1) & 7));
+  const bool nlive = 8 * gn < nnar;
+  const int cnt0 = __builtin_amdgcn_readfirstlane(cw + (nlive && (NW == 4 || wu < 4)));   // DMAs of a step, part 0
+  const int cnt1 = __builtin_amdgcn_readfirstlane(cw + (nlive && (NW == 4 || wu >= 4)));  // part 1
+  auto glds = [&](const float* src, uint32_t dst) {
+    // inline asm, as dw_big_lds's: the compiler neither counts these loads nor ties them to the LDS reads
+    uint32_t keep;
+#if SPP_DW_THIN_TIMING & 4
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+#else
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+#endif
+                 : "=&s"(keep)
+                 : "v"(src), "s"(dst)
+                 : "memory");
+  };
+  auto issue = [&](int t, int buf) {
+#pragma unroll
+    for (int p = 0; p < (kDwThinSplit ? 1 : 2); ++p) {
+      if (p == 1 && t >= n1) break;
+      const int so = __builtin_amdgcn_readfirstlane((p ? q : 0) + 32 * t);
+      const uint32_t base = (uint32_t)(size_t)(lds_void*)&lds[buf][p][0];
+#pragma unroll
+      for (int k = 0; k < WG; ++k)
+        if (8 * (WG * wu + k) < nwide) glds(srcw[k] + so, base + 1024u * (uint32_t)(WG * wu + k));
+      if (nlive && (NW == 4 || (wu >> 2) == p)) glds(srcn + so, base + 1024u * (uint32_t)(32 + gn));
+    }
+  };
+  auto issued = [&](int t) { return cnt0 + (t < n1 ? cnt1 : 0); };
+  auto wait_vm = [&](int n) {  // s_waitcnt vmcnt(n), n wave-uniform
+    static_for<0, 2 * WG + 3>([&](auto V) {
+      if (n == (int)V) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((int)V) : "memory");
+    });
+  };
+  auto barrier = [&]() {  // a bare s_barrier: __syncthreads' fence would drain the DMA in flight
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  };
+  // operand reads: LDS row offsets (floats) and swizzles of this lane's rows; rows past the last live one read row 0
+  int offw[BPW], sww[BPW];
+  bool blive[BPW], dbw[BPW];
+#pragma unroll
+  for (int bi = 0; bi < BPW; ++bi) {
+    const int blk = BPW * wu + bi, r = 32 * blk + c, R = r < nwide ? r : 0;
+    offw[bi] = 32 * R;
+    sww[bi] = (R >> 1) & 7;
+    blive[bi] = 32 * blk < nwide;
+    dbw[bi] = J.db != nullptr && (wideA || blk == 0);
+  }
+  const int rn = c < nnar ? c : 0;
+  const int offn = 32 * (256 + rn), swn = (rn >> 1) & 7;
+  // i = 2 (16-sample step of the 32) + P: piece 4 (i >> 1) + 2 h + (i & 1) of the row
+  auto rd = [&](const float* L, float4 (&wv)[BPW][4], float4 (&nv)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int pc = 4 * (i >> 1) + 2 * h + (i & 1);
+      nv[i] = *reinterpret_cast<const float4*>(L + offn + 4 * (pc ^ swn));
+#pragma unroll
+      for (int bi = 0; bi < BPW; ++bi) wv[bi][i] = *reinterpret_cast<const float4*>(L + offw[bi] + 4 * (pc ^ sww[bi]));
+    }
+  };
+  f32x16 acc[2][BPW];
+  float bs[2][BPW];
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int bi = 0; bi < BPW; ++bi) {
+      acc[p][bi] = zero16();
+      bs[p][bi] = 0.f;
+    }
+  float4 wv[2][BPW][4], nv[2][4];
+  auto mm = [&](auto WA, auto NP) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int p = 0; p < decltype(NP)::value; ++p)
+#pragma unroll
+        for (int bi = 0; bi < BPW; ++bi) {
+          if (!blive[bi]) continue;
+          const float4 av = decltype(WA)::value ? wv[p][bi][i] : nv[p][i];
+          const float4 xv = decltype(WA)::value ? nv[p][i] : wv[p][bi][i];
+          if (dbw[bi]) bs[p][bi] += (av.x + av.y) + (av.z + av.w);
+#if SPP_DW_THIN_TIMING & 2
+          acc[p][bi][i] += (av.x * xv.x + av.y * xv.y) + (av.z * xv.z + av.w * xv.w);
+#else
+          acc[p][bi] = mfma(av.x, xv.x, acc[p][bi]);
+          acc[p][bi] = mfma(av.y, xv.y, acc[p][bi]);
+          acc[p][bi] = mfma(av.z, xv.z, acc[p][bi]);
+          acc[p][bi] = mfma(av.w, xv.w, acc[p][bi]);
+#endif
+        }
+  };
+  if (n0 > 0) {
+    issue(0, 0);
+    if (n0 > 1) issue(1, 1);
+    wait_vm(n0 > 1 ? issued(1) : 0);
+    barrier();
+#pragma unroll 1
+    for (int t = 0; t < n0; ++t) {
+      const bool both = t < n1;
+      rd(lds[t & 1][0], wv[0], nv[0]);
+      if constexpr (!kDwThinSplit)
+        if (both) rd(lds[t & 1][1], wv[1], nv[1]);
+      barrier();  // every wave holds its operands of step t: buffer t & 1 is free
+#if !(SPP_DW_THIN_TIMING & 1)
+      if (t + 2 < n0) issue(t + 2, t & 1);
+#endif
+      if (wideA) {
+        if (both) mm(IC<1>{}, IC<2>{});
+        else mm(IC<1>{}, IC<1>{});
+      } else {
+        if (both) mm(IC<0>{}, IC<2>{});
+        else mm(IC<0>{}, IC<1>{});
+      }
+      if (t + 1 < n0) {
+        wait_vm(t + 2 < n0 && !(SPP_DW_THIN_TIMING & 1) ? issued(t + 2) : 0);  // this wave's rows of step t + 1 landed
+        barrier();                                // every wave's did
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < (kDwThinSplit ? 1 : 2); ++p)
+#pragma unroll
+    for (int bi = 0; bi < BPW; ++bi) {
+      if (!blive[bi]) continue;
+      const int blk = BPW * wu + bi;
+      f32x16 a1[4][1];
+      a1[0][0] = acc[p][bi];
+      const float b4[4] = {bs[p][bi], 0.f, 0.f, 0.f};
+      dw_store<1>(J, split, kDwThinSplit ? mypart : p, wideA ? blk : 0, wideA ? 0 : blk, 1, 1, dbw[bi], a1, b4);
+    }
+}
+
 }  // namespace spp

@@ -55,11 +55,15 @@ struct DwPlan {
   std::vector<int64_t> slab_off;  // per job: where its slabs start in the arena; -1: one slab, stored directly
   std::vector<int> items;         // per phase at ioff[ph]: [item_job (nitems) | item_split (nitems)]
   int ioff[2] = {0, 0}, nitems[2] = {0, 0}, nlds[2] = {0, 0};
+  int nthin[2] = {0, 0};          // trailing items of a phase that run as k_dw_thin
   int64_t max_elems[2] = {1, 1};
 };
 
 // Split assignment (written into the jobs: wsplit, split_len, nsplit), slab arena and item table of a job set.
-inline DwPlan plan_dw(std::vector<DwJob>& jobs, const int* j0, const int* nj, int nph, int Bp, int num_cu) {
+// thin_min_bp > 0: the thin fp32 jobs of a set of at least that many padded samples run as k_dw_thin (their items
+// are listed last, counted by nthin); 0: every item that is not an LDS one runs in k_dw, in the order of old.
+inline DwPlan plan_dw(std::vector<DwJob>& jobs, const int* j0, const int* nj, int nph, int Bp, int num_cu,
+                      int thin_min_bp = 0) {
   DwPlan P;
   // Sample splits: the large (>= 128x128 padded) GEMMs of a phase share ~one
   // workgroup per CU in proportion to their MACs; the small, HBM-bound ones
@@ -73,6 +77,12 @@ inline DwPlan plan_dw(std::vector<DwJob>& jobs, const int* j0, const int* nj, in
   auto lds_big = [Bp](const DwJob& j) {
     return Bp >= 8192 && j.N == 256 && j.K0 == 256 && j.K1 == 0 &&
            (!j.bf16 || (SPP_DW_BIG16 && j.a_bf && j.x_bf && Bp % 64 == 0));
+  };
+  // thin jobs (k_dw_thin): fp32, two sample parts per item, one side a single 32-block (the other at most 256)
+  auto thin_ok = [Bp, thin_min_bp](const DwJob& j) {
+    const int n32 = (int)round_up(j.N, 32), k32 = (int)round_up(j.K0 + j.K1, 32);
+    return thin_min_bp > 0 && Bp >= thin_min_bp && !j.bf16 && !j.fused && j.wsplit == 2 &&
+           ((n32 == 32 && k32 <= 256) || (k32 == 32 && n32 <= 256));
   };
   auto assign_splits = [&](int first, int count) {
     double big[2] = {0.0, 0.0};  // MACs of the large jobs per launch
@@ -114,16 +124,18 @@ inline DwPlan plan_dw(std::vector<DwJob>& jobs, const int* j0, const int* nj, in
   for (int ph = 0; ph < nph; ++ph) {
     std::vector<int> jj, ss;
     // large-GEMM items first (they set the phase's critical path): the 256 x 256 fp32 jobs (k_dw_big,
-    // LDS-DMA operands), then the other large ones, then the thin ones (k_dw)
-    P.nlds[ph] = 0;
-    for (int pass = 0; pass < 3; ++pass)
+    // LDS-DMA operands), then the other large ones, then the small ones (k_dw), then those of the small ones
+    // that k_dw_thin takes (one contiguous run at the end: k_dw's items stay contiguous too)
+    P.nlds[ph] = P.nthin[ph] = 0;
+    for (int pass = 0; pass < 4; ++pass)
       for (int j = j0[ph]; j < j0[ph] + nj[ph]; ++j) {
-        const int cls = lds_big(jobs[j]) ? 0 : (is_big(jobs[j]) ? 1 : 2);
+        const int cls = lds_big(jobs[j]) ? 0 : (is_big(jobs[j]) ? 1 : (thin_ok(jobs[j]) ? 3 : 2));
         if (cls != pass || jobs[j].fused) continue;
         for (int sp = 0; sp < jobs[j].nsplit; ++sp) {
           jj.push_back(j - j0[ph]);
           ss.push_back(sp);
           if (pass == 0) ++P.nlds[ph];
+          if (pass == 3) ++P.nthin[ph];
         }
       }
     P.max_elems[ph] = 1;

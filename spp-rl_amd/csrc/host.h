@@ -43,6 +43,8 @@ struct DwSet {
   int B = -1;
   int j0[2] = {0, 0}, nj[2] = {0, 0}, ioff[2] = {0, 0}, nitems[2] = {0, 0};
   int nlds[2] = {0, 0};  // leading items of a phase that run as k_dw_big / k_dw_big16 (256 x 256 jobs)
+  int nthin[2] = {0, 0};  // trailing items of a phase that run as k_dw_thin (thin fp32 jobs)
+  int thin_min_bp = 0;    // padded batch from which the thin jobs run as k_dw_thin; 0: never (SPP_DW_THIN, .._MIN_BP)
   int64_t max_elems[2] = {1, 1};  // reduce lanes per phase: largest [N*K | N] image x its dw_red_group
   bool bf16 = false;              // bf16 MFMA job set (k_dw<true>)
   int big_waves = 4;              // waves of the fp32 256 x 256 items' kernel: 4 k_dw_big, 8 k_dw_big8 (SPP_DW_BIG_WAVES)

@@ -10,8 +10,9 @@ namespace spp {
 // over nitems work items of jobs[0, njobs); item_job / item_split index the job table; the first
 // nlds items are 256 x 256 jobs staged through LDS (k_dw_big; bf16 sets: k_dw_big16, bf16 A and X rows), the
 // rest run in k_dw; bf16: the set's jobs are bf16 MFMA jobs (DwJob::bf16); big_waves: 8 runs the fp32 256 x 256
-// items as k_dw_big8 (two waves per SIMD), anything else as k_dw_big (bf16 sets: always k_dw_big16).
-void launch_dw_kernels(const DwJob* jobs, const int* item_job, const int* item_split, int nitems, int nlds,
+// items as k_dw_big8 (two waves per SIMD), anything else as k_dw_big (bf16 sets: always k_dw_big16).  The last
+// nthin items (fp32 sets only: plan_dw's thin jobs) run as k_dw_thin.
+void launch_dw_kernels(const DwJob* jobs, const int* item_job, const int* item_split, int nitems, int nlds, int nthin,
                        int njobs, int64_t max_elems, bool bf16, int big_waves, hipStream_t st);
 // (dw_red_group, dw_plan.h: the lanes k_dw_reduce gives one output element; max_elems counts lanes)
 

@@ -57,7 +57,7 @@ class DwJobDesc(ctypes.Structure):
     _fields_ = [("A", c_void_p), ("X0", c_void_p), ("X1", c_void_p), ("dW", c_void_p), ("db", c_void_p),
                 ("dW2", c_void_p), ("db2", c_void_p), ("slabs", c_void_p), ("N", c_int), ("K0", c_int), ("K1", c_int),
                 ("nrow2", c_int), ("bf16", c_int), ("a_bf", c_int), ("x_bf", c_int), ("fused", c_int),
-                ("nsplit", c_int), ("split_len", c_int), ("wsplit", c_int)]
+                ("nsplit", c_int), ("split_len", c_int), ("wsplit", c_int), ("thin", c_int)]
 
 
 P = ctypes.POINTER
@@ -125,6 +125,7 @@ _SIGS = {
     "sppAgentStageSplit": (c_int, [c_void_p, P(c_int)]),
     "sppAgentCriticPairs": (c_int, [c_void_p, P(c_int)]),
     "sppAgentDwBigWaves": (c_int, [c_void_p, P(c_int)]),
+    "sppAgentDwThin": (c_int, [c_void_p, P(c_int)]),
     "sppSynthEnvStep": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sppDdpgAcmUpdate": (c_int, [c_void_p, P(Batch), c_void_p, c_void_p]),
     "sppDdpgAcmCriticGrads": (c_int, [c_void_p, P(Batch), c_void_p, c_void_p]),
