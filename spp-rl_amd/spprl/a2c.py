@@ -20,18 +20,12 @@ import torch
 
 from . import config
 from ._lib import call, ptr, stream_handle
+from .onpolicy_loop import refuse_process_group
 from .ppo_vanilla import PPO
 
 # PPO.__init__'s loop / environment keywords A2C passes through
 _LOOP_KWARGS = ("iterations", "stats_freq", "test_episodes", "return_done", "max_frames", "n_envs", "env", "env_spec",
                 "device", "seed", "loop_seed")
-
-
-def refuse_process_group(owner):
-    import torch.distributed as dist
-
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise NotImplementedError("spprl.%s is single-process: data parallelism is PPO_AcM's" % owner)
 
 
 class A2C(PPO):
@@ -47,17 +41,8 @@ class A2C(PPO):
                          num_critic_updates_per_target=num_critic_updates_per_target, normalize_adv=normalize_adv,
                          obs_norm_alpha=obs_norm_alpha, batch_size=batch_size, **kw)
         self.normalize_adv = bool(normalize_adv)
-        self.loss = {"actor": 0.0, "critic": 0.0}  # a2c.py:91
 
     kl_div_updates_counter = None  # (PPO's counter: A2C has none)
-
-    def pre_train(self):
-        raise AttributeError("vanilla A2C has no ACM pre-training (rltoolkit A2C defines none)")
-
-    def update_acm(self, *a, **k):
-        raise AttributeError("vanilla A2C has no ACM (rltoolkit A2C defines none)")
-
-    update_acm_batches = update_actor_acm = update_acm
 
     def actor_observations(self, raw_obs, rollout_mean, rollout_std):
         """The observations the stored log-probs were taken on: standardize_and_clip with the ROLLOUT's statistics
@@ -73,21 +58,14 @@ class A2C(PPO):
     def update(self, mem):
         """a2c.py:137-142 on a memory dict (collect_batch's, or a caller's: PPO.update's keys; ``lp`` and ``end``
         are not read -- the log-probs are recomputed with their graph, the TD advantage needs no episode ends)."""
-        T, E, ob = mem["T"], mem.get("E", self.n_envs), self.ob_dim
-        N = T * E
-        dev = lambda t, dt=torch.float32: torch.as_tensor(t).to(self.device, dt).contiguous()  # noqa: E731
-        mem = dict(mem, obs=dev(mem["obs"]).reshape(N, ob), next_obs=dev(mem["next_obs"]).reshape(N, ob),
-                   start_obs=dev(mem["start_obs"]).reshape(-1, ob))
-        on = self.obs_norm_alpha is not None
+        _, _, N, mem = self._flatten(mem)
+        on = self.obs_norm_alpha is not None  # (the rollout's statistics, before _normalized updates them)
         rollout_mean, rollout_std = (self.obs_mean.clone(), self.obs_std.clone()) if on else (None, None)
-        if on:
-            self.update_obs_mean_std(mem)  # a2c.py:137-138
-        obs, nobs = self.normalize(mem["obs"]), self.normalize(mem["next_obs"])  # Memory.norm_obs / norm_next_obs
-        rew, done = dev(mem["rew"]).reshape(N), dev(mem["done"]).reshape(N)
+        obs, nobs, rew, done = self._normalized(mem, N)
         self.nets.update_critic(obs, nobs, rew, done, advantages=False)  # a2c.py:186-222
         adv, mom = self.nets.td_advantage(obs, nobs, rew, done)  # a2c.py:223, 227-265
         self.last_advantages = adv
         out = self.nets.pg_actor_step(self.actor_observations(mem["obs"], rollout_mean, rollout_std),
-                                      dev(mem["act"]).reshape(N, self.ac_dim), adv,
+                                      self._dev(mem["act"]).reshape(N, self.ac_dim), adv,
                                       mom if self.normalize_adv else None)  # a2c.py:267-286
         self.loss = {"actor": float(out[0].item()), "critic": self.nets.loss["critic"]}

@@ -19,7 +19,7 @@ Out of scope: data parallelism (single process), discrete actions.
 import torch
 
 from . import config
-from .a2c import refuse_process_group
+from .onpolicy_loop import refuse_process_group
 from .ppo_acm import PPO_AcM
 
 
@@ -44,17 +44,12 @@ class A2C_AcM(PPO_AcM):
 
     def update(self, mem):
         """on_policy.py:74-75: update_critic, TD advantages, one actor step on this iteration's batch."""
-        T, E, ob = mem["T"], mem.get("E", self.n_envs), self.ob_dim
-        N = T * E
-        obs = mem["obs"].reshape(N, ob)
-        raw_next = mem["next_obs"].reshape(N, ob).contiguous()
-        nobs = self.normalize(raw_next)
-        rew, done = mem["rew"].reshape(N), mem["done"].reshape(N).float()
+        _, _, N, obs, raw_next, nobs, rew, done = self._flatten(mem)
         self.nets.update_critic(obs, nobs, rew, done, advantages=False)  # a2c.py:186-222
         adv, mom = self.nets.td_advantage(obs, nobs, rew, done)  # a2c.py:223, 227-265
         self.last_advantages = adv
         mom = mom if self.normalize_adv else None
-        acts = mem["act"].reshape(N, ob)
+        acts = mem["act"].reshape(N, self.ob_dim)
         self.loss["critic"] = self.nets.loss["critic"]
         if not self.custom_loss:  # A2C.update_actor
             out = self.nets.pg_actor_step(obs, acts, adv, mom)

@@ -23,21 +23,26 @@ Vectorization: each iteration collects T = ceil(batch_size / E) steps of E locks
 (N = T*E transitions); envs keep running across iterations and the last step of every
 iteration is a truncation (end = 1, done = 0), so GAE bootstraps from V(s') there exactly as
 the reference does at a time-limit end.  With E = 1 whole episodes are collected until
-batch_size frames, as the reference does.
+batch_size frames, as the reference does.  That scheme, train, the per-step bookkeeping, test and
+save / load are OnPolicyLoop's (onpolicy_loop.py), shared with vanilla PPO; this class states its act
+call, its ring writes, the side stream, the data-parallel paths and its update.
 """
+import os
+
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from . import _lib, config
 from ._lib import call, ptr, stream_handle
+from .dp import make_allreduce
 from .onpolicy import OnPolicyNets
+from .onpolicy_loop import OnPolicyLoop
 from .ppo import calculate_gae
 from .sac_acm import SAC_AcM
-from .dp import stream_key
-from .trainer import StatsLogger, SynthVecEnv
 
 
-class PPO_AcM:
+class PPO_AcM(OnPolicyLoop):
     def __init__(self, env_name="HalfCheetah-v2", gamma=0.99, actor_lr=3e-4, critic_lr=3e-4, batch_size=2000,
                  ppo_batch_size=512, kl_div_threshold=0.1, max_ppo_epochs=10, entropy_coef=0.0, ppo_epsilon=0.2,
                  gae_lambda=0.95, critic_num_target_updates=10, num_critic_updates_per_target=10, normalize_adv=True,
@@ -59,29 +64,16 @@ class PPO_AcM:
         self.obs_norm = bool(obs_norm)
         if epsilon is not None:
             ppo_epsilon = epsilon
-        ob, ac, ac_high, max_ep = env_spec or config.ENV_SPECS[env_name]
-        self.env_name, self.ob_dim, self.ac_dim = env_name, ob, ac
-        self.device = torch.device(device)
-        self.gamma, self.gae_lambda = gamma, gae_lambda
-        self.batch_size, self.iterations, self.stats_freq = int(batch_size), int(iterations), int(stats_freq)
-        self.test_episodes, self.return_done, self.max_frames = test_episodes, return_done, max_frames
+        ac_high, max_ep, Nmax = self._init_loop(env_name, env_spec, device, gamma, gae_lambda, batch_size, iterations,
+                                                stats_freq, test_episodes, return_done, max_frames, n_envs, env,
+                                                loop_seed)
+        ob, ac, env, E = self.ob_dim, self.ac_dim, self.env, self.n_envs
         self.custom_loss, self.norm_closs = float(custom_loss), bool(norm_closs)
         self.min_max_denormalize, self.denormalize_actor_out = bool(min_max_denormalize), bool(denormalize_actor_out)
         self.acm_epochs, self.acm_update_freq, self.acm_update_batches = int(acm_epochs), acm_update_freq, \
             acm_update_batches
         self.actor_output_dim = ob
         lim = 1.0 if self.min_max_denormalize else float(config.MAX_ABS_OBS_VALUE)  # acm.py:102-108
-        if env is None:
-            env = SynthVecEnv(n_envs, ob, ac, max_episode_steps=max_ep, ac_high=ac_high, seed=loop_seed,
-                              device=self.device)
-        self.env = env
-        self.n_envs = E = env.n
-        self.T = 1 if E == 1 else max(1, -(-self.batch_size // E))
-        Nmax = max(self.T * E, self.batch_size + (max_ep or 1000) if E == 1 else 0)
-        from .dp import make_allreduce
-
-        import torch.distributed as dist
-
         dp_world = dist.get_world_size() if make_allreduce() is not None else 1  # (the union: world x N rows)
         # rehearse_world = W (measurement only, one process): update(mem) runs on this rank's rollout tiled W
         # times -- the shape, and so the per-rank work, of a W-rank job's union batch -- with no collective
@@ -91,9 +83,7 @@ class PPO_AcM:
         # all-reduce per critic / actor step (the reference's per-step losses are batch means, so equal shards
         # average to the union's gradient); "union" -- one all-gather of the rollouts per iteration and every rank
         # runs the whole update on the union (no per-step exchange, replicas equal one process on the union)
-        import os
-
-        self.dp_update = dp_update or os.environ.get("SPP_PPO_DP_UPDATE", "shard")
+        self.dp_update =dp_update or os.environ.get("SPP_PPO_DP_UPDATE", "shard")
         if self.dp_update not in ("shard", "union"):
             raise ValueError("dp_update must be 'shard' or 'union', got %r" % (self.dp_update,))
         self.nets = OnPolicyNets(ob, ob, ac_lim=lim, actor_lr=actor_lr, critic_lr=critic_lr, ppo_epsilon=ppo_epsilon,
@@ -153,24 +143,7 @@ class PPO_AcM:
         self.acm._perm_seed = int(seed or 0) * 7919 + 17  # rank-independent epoch permutations
         self._ring_log = []  # this iteration's ring writes (applied by _flush_ring)
         self._prev_all = None  # per rank: the ring slot of each env's last obs
-        self.stats_logger = StatsLogger()
-        self.iteration = 0
-        self.loop_seed, self._ctr = int(loop_seed), 0
-        self._key_policy = stream_key(loop_seed, "policy")
         self.loss = {}
-        d = self.device
-        self._ep_ret = torch.zeros(E, device=d)
-        self._ret_sums = torch.zeros(2, dtype=torch.float64, device=d)
-        self._obs = None
-        self._prev_slots = None
-
-    @property
-    def kl_div_updates_counter(self):  # ppo.py:91, on_policy.py:216 (epochs + 1 per update_actor_acm)
-        return self.nets.kl_div_updates_counter
-
-    @kl_div_updates_counter.setter
-    def kl_div_updates_counter(self, v):  # ppo.py:226 resets it after logging
-        self.nets.kl_div_updates_counter = int(v)
 
     # ---------------------------------------------------------------- helpers
     def _randn(self, t):
@@ -224,21 +197,6 @@ class PPO_AcM:
             self.replay_buffer.reset_idx()
         self._obs = None
 
-    def train(self, iterations=None):
-        if iterations:
-            self.iterations += iterations
-        while self.iteration < self.iterations:
-            ret = self.perform_iteration()
-            running = self.stats_logger.calc_running_return(ret)
-            if self.return_done is not None and running is not None and running >= self.return_done:
-                break
-            if self.test_episodes and self.iteration % self.stats_freq == 0:
-                self.stats_logger.test_return = self.test()
-            self.iteration += 1
-            if self.max_frames is not None and self.max_frames < self.stats_logger.frames:
-                break
-        return self.stats_logger.running_return
-
     def perform_iteration(self, sync=True):
         """on_policy.py:52-75.  Returns the mean return of the episodes completed (None if none).
 
@@ -273,10 +231,7 @@ class PPO_AcM:
                 self._update_acm()
         if self.denormalize_actor_out:
             self.acm.update_obs_stats()
-        if not sync:
-            return None
-        s = self._ret_sums.cpu().numpy()
-        return float(s[0] / s[1]) if s[1] > 0 else None
+        return self._mean_return(sync)
 
     def _update_acm(self):
         if self.acm_update_batches:
@@ -289,8 +244,6 @@ class PPO_AcM:
         launch per epoch), and the env var SPP_PPO_ACM_OVERLAP not 0.  Data parallel too: the iteration's
         collectives (the ring flush, the rollout union) are all issued before the side stream starts, and the
         ACM epochs themselves exchange nothing (replicated ring)."""
-        import os
-
         if os.environ.get("SPP_PPO_ACM_OVERLAP", "1") == "0" or self.device.type != "cuda":
             return None
         if not self.acm._acm_sgd_ok(self.acm.acm_batch_size):
@@ -301,10 +254,8 @@ class PPO_AcM:
 
     # ---------------------------------------------------------------- A2C.collect_batch
     def _start(self):
-        self._obs = self.env.reset()
+        super()._start()
         self._ring_log.append(("start", self._obs.clone()))
-        self._ep_ret.zero_()
-        self._ep_len = np.zeros(self.n_envs, np.int64)
 
     # ---------------------------------------------------------------- the ACM ring (add_buffer)
     def _flush_ring(self):
@@ -323,8 +274,6 @@ class PPO_AcM:
             # (a rehearsal of R ranks: the replicated ring takes R ranks' writes per iteration -- this rank's R times)
             blocks = [log] * R
         else:
-            import torch.distributed as dist
-
             F = 2 * ob + ac + 4  # obs | rew | done | end | env action | reset obs | reset mask
             buf = torch.zeros(len(log), E, F, device=self.device)
             for i, rec in enumerate(log):
@@ -375,72 +324,29 @@ class PPO_AcM:
                     prev[idx] = rs
             self._prev_all[r] = prev
 
-    def collect_batch(self):
+    def _memory(self, flat):
         """Rollout memory, time-major [T][E]: normalised obs, actions, log-probs, rewards, done,
-        end, next obs (raw)."""
-        E = self.n_envs
-        if E == 1:  # whole episodes until batch_size frames (a2c.py:155-184)
-            steps = []
-            while sum(len(s) for s in steps) < self.batch_size:
-                self.stats_logger.rollouts += 1
-                self._start()
-                seg, end = [], False
-                while not end:
-                    step = self._step()
-                    end = bool(step[-1])
-                    seg.append(step[:-1])
-                steps.append(seg)
-            flat = [x for s in steps for x in s]
-        else:
-            if self._obs is None:
-                self._start()
-                self.stats_logger.rollouts += E
-            flat = [self._step()[:-1] for _ in range(self.T)]
+        end, next obs (raw).  The iteration's ring writes are applied first."""
         self._flush_ring()
-        T = len(flat)
-        cat = lambda k: torch.stack([f[k] for f in flat])  # noqa: E731
-        mem = {"obs": cat(0), "act": cat(1), "lp": cat(2), "rew": cat(3), "done": cat(4), "end": cat(5),
-               "next_obs": cat(6), "T": T}
-        if E > 1:
-            mem["end"][-1].fill_(1)  # segment truncation: GAE bootstraps from V(s') (ppo.py:136-148)
-        self.stats_logger.frames += T * E
-        return mem
+        return super()._memory(flat)
 
     def _step(self):
-        E, rb = self.n_envs, self.replay_buffer
         norm_obs = self.normalize(self._obs)
-        eps = self._randn(torch.empty(E, self.actor_output_dim, device=self.device))
+        eps = self._randn(torch.empty(self.n_envs, self.actor_output_dim, device=self.device))
         act, lp = self.nets.act(norm_obs, eps)
         env_act = self.process_action(act, norm_obs)
         nobs, rew, end, end_dev = self.env.step(env_act)
-        # a2c.py:168-171: end = env done; done = False when the episode hit max_ep_len (a time-limit end)
-        self._ep_len += 1
-        max_ep = getattr(self.env, "_max_episode_steps", None)
-        done_h = end & (self._ep_len != max_ep) if max_ep else end.copy()
-        self._ep_len[end] = 0
-        done = (torch.from_numpy(done_h.astype(np.uint8)).to(self.device) if done_h.any()
-                else torch.zeros(E, dtype=torch.uint8, device=self.device))
-        any_end = bool(end.any())
-        call("sppEpisodeAccum", ptr(rew), ptr(end_dev) if any_end else None, E, ptr(self._ep_ret),
-             ptr(self._ret_sums), stream_handle())
-        out = (norm_obs, act, lp, rew.clone(), done, end_dev.clone(), nobs.clone(), end.any() if E == 1 else False)
-        self._obs = nobs
-        mask, robs = None, None
-        if any_end and E > 1:
-            self.stats_logger.rollouts += int(end.sum())
-            self._obs = self.env.reset(end)
-            mask, robs = end.copy(), self._obs.clone()
+        tail, reset = self._account(nobs, rew, end, end_dev)
+        mask, robs = (end.copy(), self._obs.clone()) if reset else (None, None)
         # ring writes of this step (applied at the iteration's end, _flush_ring)
-        self._ring_log.append(("step", out[6], out[3], done, out[5], env_act.clone(), mask, robs))
-        return out
+        self._ring_log.append(("step", tail[3], tail[0], tail[1], tail[2], env_act.clone(), mask, robs))
+        return (norm_obs, act, lp) + tail
 
     # ---------------------------------------------------------------- data parallel: the rollout union
     def _union(self, mem):
         """All-gather the ranks' rollouts [T][E] into the union [T][world * E] (rank-major along the env axis),
         in one collective of one packed tensor: normalised obs | action | log-prob | reward | done | end | next
         obs.  Every rank then holds the same batch."""
-        import torch.distributed as dist
-
         if mem.get("union"):
             return mem
         T, E, ob, W = mem["T"], self.n_envs, self.ob_dim, self.world
@@ -468,22 +374,26 @@ class PPO_AcM:
                 "union": True}
 
     # ---------------------------------------------------------------- update (critic, GAE, actor)
+    def _flatten(self, mem):
+        """(T, E, N = T * E, obs [N][ob], the raw and the normalised next obs [N][ob], rew [N], done [N] float)."""
+        T, E, ob = mem["T"], mem.get("E", self.n_envs), self.ob_dim
+        N = T * E
+        raw_next = mem["next_obs"].reshape(N, ob).contiguous()
+        return (T, E, N, mem["obs"].reshape(N, ob), raw_next, self.normalize(raw_next), mem["rew"].reshape(N),
+                mem["done"].reshape(N).float())
+
     def update(self, mem):
         """critic, GAE, actor on the iteration's batch: this rank's rollout, or (data parallel) the union of every
         rank's (self._union; a caller may pass the union itself)."""
         if self.dp and self.dp_update == "union":
             mem = self._union(mem)
-        T, E, ob = mem["T"], mem.get("E", self.n_envs), self.ob_dim
-        N = T * E
-        obs = mem["obs"].reshape(N, ob)
-        nobs = self.normalize(mem["next_obs"].reshape(N, ob))
-        rew, done = mem["rew"].reshape(N), mem["done"].reshape(N).float()
+        T, E, N, obs, _, nobs, rew, done = self._flatten(mem)
         self.nets.update_critic(obs, nobs, rew, done)  # a2c.py:186-225
         v = self.nets.value(obs).reshape(T, E)
         v_next = self.nets.value(nobs).reshape(T, E)
         _, adv = calculate_gae(mem["rew"].reshape(T, E), v, v_next, mem["done"].reshape(T, E),
                                mem["end"].reshape(T, E), self.gamma, self.gae_lambda)
-        acts = mem["act"].reshape(N, ob)
+        acts = mem["act"].reshape(N, self.ob_dim)
         nxt = nobs
         if not self.norm_closs:  # on_policy.py:191-193
             nxt, acts = self.denormalize(nobs), self.denormalize(acts)
@@ -492,50 +402,17 @@ class PPO_AcM:
         self.loss["acm"] = None
 
     # ---------------------------------------------------------------- test (a2c.py test)
-    def test(self, episodes=None):
-        episodes = episodes or self.test_episodes or 1
-        env = self.env.spawn(episodes, seed=self.loop_seed + 99991)
-        obs = env.reset()
-        ret = torch.zeros(episodes, device=self.device)
-        sums = torch.zeros(2, dtype=torch.float64, device=self.device)
-        alive = np.ones(episodes, bool)
-        while alive.any():
-            n_obs = self.normalize(obs)
-            act, _ = self.nets.act(n_obs, None)  # deterministic mean
-            obs, rew, end, _ = env.step(self.process_action(act, n_obs))
-            m = torch.as_tensor((end & alive).astype(np.uint8), device=self.device)
-            call("sppEpisodeAccum", ptr(rew), ptr(m), episodes, ptr(ret), ptr(sums), stream_handle())
-            alive &= ~end
-            if end.any() and alive.any():
-                obs = env.reset(end)
-        s = sums.cpu().numpy()
-        return float(s[0] / s[1])
+    def _test_action(self, obs):
+        n_obs = self.normalize(obs)
+        act, _ = self.nets.act(n_obs, None)  # deterministic mean
+        return self.process_action(act, n_obs)
 
-    # ---------------------------------------------------------------- checkpoints (rl.py:263-301)
+    # ---------------------------------------------------------------- checkpoints (rl.py:263-279 + ACM)
     def collect_params_dict(self):
-        from .onpolicy import actor_layout, critic_layout
-        from . import nets as _nets
+        return {**self._nets_state(), **self.replay_buffer.normalizer_state(),
+                "acm": self.acm.net_state(_lib.SPP_NET_ACM)}
 
-        return {"actor": _nets.state_dict(self.nets.params[0], actor_layout(self.ob_dim, self.ob_dim)),
-                "critic": _nets.state_dict(self.nets.params[1], critic_layout(self.ob_dim)),
-                **self.replay_buffer.normalizer_state(), "acm": self.acm.net_state(_lib.SPP_NET_ACM)}
-
-    def apply_params_dict(self, d):  # rl.py:263-279 + ACM (acm/on_policy.py)
-        from .onpolicy import actor_layout, critic_layout
-        from . import nets as _nets
-
-        for i, (k, lay) in enumerate((("actor", actor_layout(self.ob_dim, self.ob_dim)),
-                                      ("critic", critic_layout(self.ob_dim)))):
-            _nets.load_state(self.nets.params[i], lay, d[k])
+    def apply_params_dict(self, d):  # (acm/on_policy.py)
+        self._load_nets(d)
         self.acm.load_net(_lib.SPP_NET_ACM, d["acm"])
         self.replay_buffer.load_normalizer_state(d)
-
-    def save(self, path):  # rl.py:281-292
-        from .checkpoint import save_params
-
-        save_params(path, self.collect_params_dict())
-
-    def load(self, path):  # rl.py:294-301
-        from .checkpoint import load_params
-
-        self.apply_params_dict(load_params(path))

@@ -158,7 +158,7 @@ def test_a2c_acm_refuses_ppo_keywords(kw, monkeypatch):
 
 
 def test_a2c_keywords_reach_the_library(monkeypatch):
-    from spprl import _lib, ppo_vanilla, trainer
+    from spprl import _lib, onpolicy_loop, trainer
 
     class Reached(Exception):
         pass
@@ -169,7 +169,7 @@ def test_a2c_keywords_reach_the_library(monkeypatch):
     monkeypatch.setattr(_lib, "load", stop)
     monkeypatch.setattr(_lib, "call", stop)
     monkeypatch.setattr(trainer, "SynthVecEnv", stop)
-    monkeypatch.setattr(ppo_vanilla, "SynthVecEnv", stop)
+    monkeypatch.setattr(onpolicy_loop, "SynthVecEnv", stop)
     with pytest.raises(Reached):
         spprl.A2C(device="cpu", env_name="Hopper-v2", iterations=10, gamma=0.99, actor_lr=3e-4, critic_lr=1e-3,
                   batch_size=2000, tensorboard_dir="logs", log_dir="logs/basic_logs", verbose=0, render=False,

@@ -99,7 +99,7 @@ TRAIN_KW = dict(iterations=1001, gamma=0.99, actor_lr=3e-4, critic_lr=1e-3, batc
 
 def test_training_script_keywords_reach_the_library(monkeypatch):
     """Every keyword is accepted up to the point where the library would be loaded."""
-    from spprl import _lib, ppo_vanilla, trainer
+    from spprl import _lib, onpolicy_loop, trainer
 
     class Reached(Exception):
         pass
@@ -110,7 +110,7 @@ def test_training_script_keywords_reach_the_library(monkeypatch):
     monkeypatch.setattr(_lib, "load", stop)
     monkeypatch.setattr(_lib, "call", stop)
     monkeypatch.setattr(trainer, "SynthVecEnv", stop)
-    monkeypatch.setattr(ppo_vanilla, "SynthVecEnv", stop)
+    monkeypatch.setattr(onpolicy_loop, "SynthVecEnv", stop)
     with pytest.raises(Reached):
         spprl.PPO(device="cpu", **TRAIN_KW)
 
