@@ -370,6 +370,12 @@ sppStatus sppAgentStageSplit(sppAgentHandle h, int* bits_out);
  * under SPP_CRITIC_PAIRS=0 (read at creation; the default is 1, and 3 asks for both).  The small-batch team
  * kernels are not paired. */
 sppStatus sppAgentCriticPairs(sppAgentHandle h, int* bits_out);
+/* Which actor trunk kernels of this SAC_AcM handle hand the small layer's output to the 256-wide layer in registers
+ * instead of through the LDS image (bit 0: both trunk forward kernels, behind stage-split cuts 2 / 3; bit 1: the trunk
+ * backward, behind cut 1), as SPP_ACTOR_GEN asked when the agent was created; 0 for handles without those cuts or
+ * kernels (wide observations or heads, mlp_bf16, DDPG_AcM, the vanilla algorithms).  The results of both forms are
+ * identical bit for bit. */
+sppStatus sppAgentActorGen(sppAgentHandle h, int* bits_out);
 /* Waves per workgroup of the kernel that runs this handle's fp32 256 x 256 weight-gradient items (batches of 8,192
  * padded samples and more): 8 (k_dw_big8, two waves per SIMD) or 4 (k_dw_big), as SPP_DW_BIG_WAVES asked when the
  * agent was created (the default is 8); always 4 for mlp_bf16 handles, whose items run in the 4-wave k_dw_big16.

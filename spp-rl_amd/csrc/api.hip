@@ -782,6 +782,10 @@ struct sppAgent {
   //   bit 0  k_sac_critic_phase<C, true>      -> <C, true, true>        (behind stage-split cut 3)
   //   bit 1  k_sac_actor_phase<C, true, true> -> <C, true, true, true>  (behind stage-split cut 2)
   int critic_pairs = 0;
+  // register hand-over forms of the actor trunk kernels (sac.hip), one bit per direction; SPP_ACTOR_GEN=0: the staged kernels (A/B).
+  //   bit 0  k_sac_trunk_fwd<C, ACT>  -> k_sac_trunk_fwd_gen<C, ACT>     (each behind its stage-split cut, 2 / 3)
+  //   bit 1  k_sac_actor_trunk_bwd    -> k_sac_actor_trunk_bwd_gen       (behind stage-split cut 1)
+  int actor_gen = 0;
   float *THD = nullptr, *SCA = nullptr, *SLP = nullptr;  // its hand-overs (SacArgs)
   AcmScratch mq{};  // its hand-over buffers (SEL ... DCA)
   // ACM regression scratch
@@ -1168,6 +1172,7 @@ static void launch_adam(sppAgent* a, int first, int count, int64_t n, int64_t st
 constexpr int kStageWGPerCU = 3;
 constexpr int kStageSplitAll = 7;
 constexpr int kStageSplitDefault = kStageSplitAll;
+constexpr int kActorGenDefault = 3;  // both bits cleared the bench rule
 constexpr int kCriticPairsDefault = 1;  // bit 1 measured inside the run-to-run range: off unless asked for
 constexpr int kDwBigWavesDefault = 8;
 // The padded batch from which a job set's thin fp32 weight gradients run as k_dw_thin (dw.hip), 0: never.
@@ -1311,6 +1316,12 @@ sppStatus sppAgentCreate(sppAgentHandle* out, const sppAgentConfig* cfg, int dev
     const int wantp = cp ? atoi(cp) : kCriticPairsDefault;
     if ((a->stage_split & 4) && ks.critic_rest_pair) a->critic_pairs |= wantp & 1;
     if ((a->stage_split & 2) && ks.critics_a_pair) a->critic_pairs |= wantp & 2;
+    // SAC_AcM handles (the vanilla handles train at team-kernel batch sizes)
+    const char* ag = getenv("SPP_ACTOR_GEN");
+    const int wantg = ag ? atoi(ag) : kActorGenDefault;
+    const bool acm = cfg->algo == SPP_ALGO_SAC_ACM;
+    if (acm && (a->stage_split & 6) && ks.trunk_fwd_a_gen && ks.trunk_fwd_c_gen) a->actor_gen |= wantg & 1;
+    if (acm && (a->stage_split & 1) && ks.trunk_bwd_gen) a->actor_gen |= wantg & 2;
     // waves of the fp32 256 x 256 weight-gradient kernel (dw.hip): 8 = k_dw_big8, 4 = k_dw_big; the bf16 sets'
     // k_dw_big16 has 4
     const char* bw = getenv("SPP_DW_BIG_WAVES");
@@ -1520,7 +1531,7 @@ static sppStatus critic_grads_staged(sppAgentHandle a, float* losses, hipStream_
   const bool team = phase_team(a, p.Bp);
   if (!team && (a->stage_split & 4)) {
     // stage split: the target actor's trunk; the squash and the ACM forward; both target critics and the critics
-    hipLaunchKernelGGL(a->ks.trunk_fwd_c, dim3(tile_grid(a, p.Bp)), dim3(256), 0, st, p, a->mq);
+    hipLaunchKernelGGL((a->actor_gen & 1) ? a->ks.trunk_fwd_c_gen : a->ks.trunk_fwd_c, dim3(tile_grid(a, p.Bp)), dim3(256), 0, st, p, a->mq);
     hipLaunchKernelGGL(a->ks.squash_c, dim3(stage_grid(a, p.Bp)), dim3(256), 0, st, stage_args(a, p), a->mq);
     hipLaunchKernelGGL((a->critic_pairs & 1) ? a->ks.critic_rest_pair : a->ks.critic_rest, dim3(grid), dim3(256), 0, st, p);
   } else {
@@ -1577,7 +1588,7 @@ static sppStatus actor_grads(sppAgentHandle a, float* losses, hipStream_t st) {
     // backward over the regrouped samples; everything behind it in the original order (sac.hip)
     z = a->mq;
     if (a->stage_split & 2) {
-      hipLaunchKernelGGL(a->ks.trunk_fwd_a, dim3(grid), dim3(256), 0, st, p, z);
+      hipLaunchKernelGGL((a->actor_gen & 1) ? a->ks.trunk_fwd_a_gen : a->ks.trunk_fwd_a, dim3(grid), dim3(256), 0, st, p, z);
       hipLaunchKernelGGL(a->ks.squash_a, dim3(stage_grid(a, p.Bp)), dim3(256), 0, st, stage_args(a, p), z);
       hipLaunchKernelGGL((a->critic_pairs & 2) ? a->ks.critics_a_pair : a->ks.critics_a, dim3(grid), dim3(256), 0, st, p, z);
     } else {
@@ -1589,7 +1600,7 @@ static sppStatus actor_grads(sppAgentHandle a, float* losses, hipStream_t st) {
     hipLaunchKernelGGL(a->ks.actor_minq, dim3(grid), dim3(256), 0, st, p, z);
     if (a->stage_split & 1) {
       hipLaunchKernelGGL(a->ks.heads_stage, dim3(stage_grid(a, p.Bp)), dim3(256), 0, st, stage_args(a, p), z);
-      hipLaunchKernelGGL(a->ks.trunk_bwd, dim3(grid), dim3(256), 0, st, p, z);
+      hipLaunchKernelGGL((a->actor_gen & 2) ? a->ks.trunk_bwd_gen : a->ks.trunk_bwd, dim3(grid), dim3(256), 0, st, p, z);
     } else {
       hipLaunchKernelGGL(a->ks.actor_bwd, dim3(grid), dim3(256), 0, st, p, z);
     }
@@ -1629,6 +1640,12 @@ sppStatus sppAgentStageSplit(sppAgentHandle a, int* bits_out) {
 sppStatus sppAgentCriticPairs(sppAgentHandle a, int* bits_out) {
   SPP_REQUIRE(a && bits_out, SPP_E_INVALID_ARG, "null");
   *bits_out = a->critic_pairs;
+  return SPP_OK;
+}
+
+sppStatus sppAgentActorGen(sppAgentHandle a, int* bits_out) {
+  SPP_REQUIRE(a && bits_out, SPP_E_INVALID_ARG, "null");
+  *bits_out = a->actor_gen;
   return SPP_OK;
 }
 

@@ -28,9 +28,12 @@
 // hand-over, so each can be A/B'd on its own; 0 compiles the staged code.
 //   1  critic phase: delta2 -> W2^T      2  actor phase: each critic's delta2 -> W2^T
 //   4  critic_forward: fc1 -> fc2
-// (The actor trunk's fc1 -> fc2 was tried as a fourth bit and is not shipped: DESIGN.md §8.)
+//   8  k_sac_trunk_fwd_gen: the actor's fc1 -> fc2      16  k_sac_actor_trunk_bwd_gen: Wh^T -> W2^T
+// Bits 8 and 16 compile kernels of their own beside the staged ones (chosen per handle, SPP_ACTOR_GEN); every
+// other caller of actor_trunk keeps the staged path.  (The actor trunk's fc1 -> fc2 for every caller was tried
+// in round 7 and is not shipped: DESIGN.md §8.)
 #ifndef SPP_GEN_INPUTS
-#define SPP_GEN_INPUTS 7
+#define SPP_GEN_INPUTS 31
 #endif
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

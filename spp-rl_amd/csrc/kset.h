@@ -49,6 +49,11 @@ struct KernelSet {
   // wave-pair forms of critics_a and critic_rest (sac.hip): a tile's two critics on two waves
   void (*critics_a_pair)(SacArgs, AcmScratch);
   void (*critic_rest_pair)(SacArgs);
+  // register hand-over forms of the three trunk kernels (sac.hip: Fc1Gen / WhTGen under the 256-wide layer; SPP_ACTOR_GEN);
+  // null where the set compiles none (Cfg::GEN_AFC1 / GEN_AWHT)
+  void (*trunk_fwd_a_gen)(SacArgs, AcmScratch);
+  void (*trunk_fwd_c_gen)(SacArgs, AcmScratch);
+  void (*trunk_bwd_gen)(SacArgs, AcmScratch);
 };
 
 template <int OB, int AOUT, int AC, bool ACMC, bool BF = false>
@@ -77,6 +82,11 @@ KernelSet make_kset() {
       ks.critic_rest = k_sac_critic_phase<C, true>;
       ks.critics_a_pair = k_sac_actor_phase<C, true, true, true>;
       ks.critic_rest_pair = k_sac_critic_phase<C, true, true>;
+      if constexpr (C::GEN_AFC1) {
+        ks.trunk_fwd_a_gen = k_sac_trunk_fwd_gen<C, true>;
+        ks.trunk_fwd_c_gen = k_sac_trunk_fwd_gen<C, false>;
+      }
+      if constexpr (C::GEN_AWHT) ks.trunk_bwd_gen = k_sac_actor_trunk_bwd_gen<C>;
     }
   }
   return ks;

@@ -51,6 +51,10 @@ struct Cfg {
   static constexpr bool GEN_CD2 = kGenOk && (SPP_GEN_INPUTS & 1);   // critic phase: delta2 -> W2^T
   static constexpr bool GEN_AD2 = kGenOk && (SPP_GEN_INPUTS & 2);   // actor phase: delta2 -> W2^T
   static constexpr bool GEN_CFC1 = kGenOk && (SPP_GEN_INPUTS & 4);  // critic_forward: fc1 -> fc2
+  // the stage split's trunk kernels only (selected per call site: with the actor's generator beside the
+  // critics' the one-kernel phases spill); the narrow heads those kernels exist for
+  static constexpr bool GEN_AFC1 = kGenOk && NB_PAIR <= 2 && (SPP_GEN_INPUTS & 8);   // k_sac_trunk_fwd_gen: fc1 -> fc2
+  static constexpr bool GEN_AWHT = kGenOk && NB_PAIR <= 2 && (SPP_GEN_INPUTS & 16);  // k_sac_actor_trunk_bwd_gen: Wh^T -> W2^T
   static_assert(AC <= 32, "env action dim <= 32");
   static_assert(2 * AOUT <= 256 && OB + AOUT <= 256, "dims");
 };
@@ -353,47 +357,123 @@ struct Fc1Gen {
   }
 };
 
+// dh2 = Wh^T dheads * relu'(h2) of the actor trunk's backward, a register-input layer without a bias
+// (dense_impl's chain with a null bias table: zero16(), then the register quads in flat order), as the
+// input of W2^T.  Parts as Fc1Gen: part 0 runs block ib's MFMA chain and requests block ib+1's
+// fragments; the other parts spread the h2 mask select and st(unit row, value), the AD2 operand store.
+template <int NBI, uint64_t RV, int NP, typename St>
+struct WhTGen {
+  static constexpr int NQ = rv_total(RV, NBI);
+  static constexpr int OBSTRIDE = NBI * 4 * 64 * 16;  // bytes per output block
+  const f32x16 (&in)[NBI];
+  rsrc_t wr;
+  uint32_t l16;
+  uint64_t lo, hi;
+  St st;
+  float4 cur[NQ];
+  f32x16 acc;
+  __device__ __forceinline__ void request(int ob) {
+    const int wn = ob * OBSTRIDE;
+    static_for<0, NQ>([&](auto Q) {
+      constexpr int q = Q;
+      cur[q] = wfrag(wr, l16, wn + (q_ib(RV, NBI, q) * 4 + q_rq(RV, NBI, q)) * 1024);
+    });
+  }
+  template <int P>
+  __device__ __forceinline__ void operator()(int ib, IC<P>, f32x16& x) {
+    if constexpr (P == 0) {
+      acc = zero16();
+      static_for<0, NQ>([&](auto Q) {
+        constexpr int q = Q;
+        constexpr int kb = q_ib(RV, NBI, q);
+        constexpr int rq = q_rq(RV, NBI, q);
+        acc = mfma(cur[q].x, in[kb][4 * rq + 0], acc);
+        acc = mfma(cur[q].y, in[kb][4 * rq + 1], acc);
+        acc = mfma(cur[q].z, in[kb][4 * rq + 2], acc);
+        acc = mfma(cur[q].w, in[kb][4 * rq + 3], acc);
+      });
+      request(ib + 1 < 8 ? ib + 1 : ib);  // (the last block re-reads its own: no branch in the MFMA loop)
+    } else {
+#pragma unroll
+      for (int q = gen_q0(P, NP); q < gen_q0(P + 1, NP); ++q) {
+        const float v = getbit(lo, hi, ib, q) ? acc[q] : 0.f;
+        x[q] = v;
+        st(32 * ib + ru(q), v);
+      }
+    }
+  }
+};
+
 // Actor trunk: x -> relu(L1) -> relu(L2) -> heads into LDS rows [0, NHR): SAC
 // (mu | logsig), NHR = 2*AOUT; DDPG fc3 pre-activation, NHR = AOUT (NBH blocks).
 // ST: store h1 / h2 feature-major (H1g, H2g).  Returns the ReLU masks.
 // HG: the heads go feature-major to HDg [NHR][ld] at the sample's own column instead of into the image.
-template <class C, bool ST, int NBH = C::NB_H2, int NHR = 2 * C::AOUT, bool HG = false>
+// GEN: fc1's blocks are produced in registers under fc2's MFMAs (Fc1Gen, as critic_forward's); fc1 does not
+// touch the image.  Off by default: a flag of the call site, not of the kernel set (Cfg::GEN_AFC1).
+template <class C, bool ST, int NBH = C::NB_H2, int NHR = 2 * C::AOUT, bool HG = false, bool GEN = false>
 __device__ __forceinline__ void actor_trunk(const ActorDev& A, const float* X, int xbytes, const Lane& L, float* H1g,
                                             float* H2g,
                                             uint64_t& m1lo, uint64_t& m1hi, uint64_t& m2lo, uint64_t& m2hi,
                                             float* HDg = nullptr) {
-  {
+  if constexpr (GEN) {
+    static_assert(!C::BF, "fp32 sets");
     f32x16 x[C::NB_OB];
     gm_load<C::NB_OB>(x, X, xbytes, C::OB, L.ld4, L.vo);
-    const rsrc_t hr = rsrc(H1g);
-    dense<C::NB_OB, C::RV_X, C::BF>(A.W1, 8, x, L.tbl + A.tb1, [&](int ob, const f32x16& acc) {
+    const rsrc_t h1r = rsrc(H1g), h2r = rsrc(H2g);
+    const int ld4 = L.ld4;
+    const uint32_t vo = L.vo;
+    auto st1 = [=](int ur, float v) {
+      if constexpr (ST) op_st<C::BF>(h1r, ur, ld4, vo, v);
+    };
+    Fc1Gen<C::NB_OB, C::RV_X, 8, decltype(st1)> g{x, rsrc(A.W1), 16u * lane_id(), L.tbl + A.tb1, L.h, m1lo, m1hi, st1};
+    g.request(0);
+    SPP_TP(1);
+    dense_gen<8>(A.W2, L.tbl + A.tb2, g, [&](int ob, const f32x16& acc) {
       uint32_t bits = 0;
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int ur = 32 * ob + ru(q);
         const float v = fmaxf(acc[q], 0.f);
         L.bl[ur * 32] = v;
-        if constexpr (ST) op_st<C::BF>(hr, ur, L.ld4, L.vo, v);
-        bits |= (uint32_t)(v > 0.f) << q;
-      }
-      setbits(m1lo, m1hi, ob, bits);
-    });
-  }
-  SPP_TP(1);
-  {
-    const rsrc_t hr = rsrc(H2g);
-    dense_lds<8, C::BF>(A.W2, L.img, L.tbl + A.tb2, [&](int ob, const f32x16& acc) {
-      uint32_t bits = 0;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int ur = 32 * ob + ru(q);
-        const float v = fmaxf(acc[q], 0.f);
-        L.bl[ur * 32] = v;
-        if constexpr (ST) op_st<C::BF>(hr, ur, L.ld4, L.vo, v);
+        if constexpr (ST) op_st<C::BF>(h2r, ur, L.ld4, L.vo, v);
         bits |= (uint32_t)(v > 0.f) << q;
       }
       setbits(m2lo, m2hi, ob, bits);
     });
+  } else {
+    {
+      f32x16 x[C::NB_OB];
+      gm_load<C::NB_OB>(x, X, xbytes, C::OB, L.ld4, L.vo);
+      const rsrc_t hr = rsrc(H1g);
+      dense<C::NB_OB, C::RV_X, C::BF>(A.W1, 8, x, L.tbl + A.tb1, [&](int ob, const f32x16& acc) {
+        uint32_t bits = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int ur = 32 * ob + ru(q);
+          const float v = fmaxf(acc[q], 0.f);
+          L.bl[ur * 32] = v;
+          if constexpr (ST) op_st<C::BF>(hr, ur, L.ld4, L.vo, v);
+          bits |= (uint32_t)(v > 0.f) << q;
+        }
+        setbits(m1lo, m1hi, ob, bits);
+      });
+    }
+    SPP_TP(1);
+    {
+      const rsrc_t hr = rsrc(H2g);
+      dense_lds<8, C::BF>(A.W2, L.img, L.tbl + A.tb2, [&](int ob, const f32x16& acc) {
+        uint32_t bits = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int ur = 32 * ob + ru(q);
+          const float v = fmaxf(acc[q], 0.f);
+          L.bl[ur * 32] = v;
+          if constexpr (ST) op_st<C::BF>(hr, ur, L.ld4, L.vo, v);
+          bits |= (uint32_t)(v > 0.f) << q;
+        }
+        setbits(m2lo, m2hi, ob, bits);
+      });
+    }
   }
   SPP_TP(2);
   {
@@ -1017,6 +1097,24 @@ __device__ __forceinline__ void actor_trunk_backward(const SacArgs& p, const Lan
       op_st<C::BF>(rsrc(p.AD1), 32 * ob + ru(q), L.ld4, L.vo, getbit(a1lo, a1hi, ob, q) ? acc[q] : 0.f);
   });
 }
+// The same with dh2's blocks produced in registers under the W2^T MFMAs (WhTGen): no LDS image at all.
+template <class C>
+__device__ __forceinline__ void actor_trunk_backward_gen(const SacArgs& p, const Lane& L,
+                                                         const f32x16 (&hd)[C::NB_PAIR], uint64_t a1lo, uint64_t a1hi,
+                                                         uint64_t a2lo, uint64_t a2hi) {
+  static_assert(!C::BF, "fp32 sets");
+  const rsrc_t d2r = rsrc(p.AD2);
+  const int ld4 = L.ld4;
+  const uint32_t vo = L.vo;
+  auto st2 = [=](int ur, float v) { op_st<C::BF>(d2r, ur, ld4, vo, v); };
+  WhTGen<C::NB_PAIR, C::RV_PAIR, 8, decltype(st2)> g{hd, rsrc(p.actor.WhT), 16u * lane_id(), a2lo, a2hi, st2};
+  g.request(0);
+  dense_gen<8>(p.actor.W2T, nullptr, g, [&](int ob, const f32x16& acc) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+      op_st<C::BF>(rsrc(p.AD1), 32 * ob + ru(q), L.ld4, L.vo, getbit(a1lo, a1hi, ob, q) ? acc[q] : 0.f);
+  });
+}
 
 // SPLIT (the min-critic split, fp32 sets): the kernel ends after q = min(Q1, Q2) and hands the rest of the
 // phase to k_sac_minq_backward (the chosen critic's backward, samples regrouped by critic) and
@@ -1404,6 +1502,11 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_heads(SacArgs p, AcmScratc
 //  k_sac_squash_stage<C, ACT>   the squash from those rows and eps, the ACM forward; the critics' action input
 //                               goes to p.SCA [CA][Bp] and log pi to p.SLP [Bp]
 //  k_sac_actor_phase<C, true, true> / k_sac_critic_phase<C, true>   the rest of the phase from S | SCA and SLP
+//
+// The three trunk kernels have register hand-over forms (k_sac_trunk_fwd_gen<C, ACT>: Fc1Gen under fc2;
+// k_sac_actor_trunk_bwd_gen: WhTGen under W2^T, no LDS at all), chosen per handle (SPP_ACTOR_GEN, api.hip); the
+// generators run the staged layers' MFMA chains, so every array is bit-identical here too.
+
 // floats: the ACM's three bias vectors (64 + 32 + 32) and actor_lim, acm_lim, n0, n1 (32 each: aout, ac <= 32)
 constexpr int kStageTab = 256;
 
@@ -1463,14 +1566,30 @@ __global__ __launch_bounds__(256, 1) void k_sac_actor_trunk_bwd(SacArgs p, AcmSc
   }
   SPP_TP_FLUSH();
 }
-
-template <class C, bool ACT>
-__global__ __launch_bounds__(256, 1) void k_sac_trunk_fwd(SacArgs p, AcmScratch z) {
-  static_assert(C::NB_PAIR <= 2 && !C::BF, "narrow heads, fp32");
-  __shared__ float smem[kWavesPerWG * kLdsPerWave];
-  __shared__ __attribute__((aligned(16))) float tbl[kTabMax];
+// k_sac_actor_trunk_bwd with Wh^T's blocks handed to W2^T in registers (Cfg::GEN_AWHT): no LDS image, no table
+template <class C>
+__global__ __launch_bounds__(256, 1) void k_sac_actor_trunk_bwd_gen(SacArgs p, AcmScratch z) {
+  static_assert(C::GEN_AWHT, "narrow heads, fp32, one observation block");
   SPP_TP_INIT();
-  load_table(p, tbl);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int ntiles = p.Bp / 32;
+  const int ld = p.Bp;
+  for (int tile = blockIdx.x * kWavesPerWG + w; tile < ntiles; tile += gridDim.x * kWavesPerWG) {
+    const Lane L = make_lane(nullptr, nullptr, nullptr, ld, tile * 32 + (lane & 31));
+    const uint64_t* mk = z.MASK + (int64_t)tile * 4 * 64 + lane;
+    const uint64_t a1lo = mk[0], a1hi = mk[64], a2lo = mk[128], a2hi = mk[192];
+    f32x16 hd[C::NB_PAIR];
+    load_pair_gl<C>(hd, p.ADH, L.ld4, L.vp);
+    SPP_TP(17);  // heads backward (here: its results read back)
+    actor_trunk_backward_gen<C>(p, L, hd, a1lo, a1hi, a2lo, a2hi);
+    SPP_TP(18);  // trunk backward
+  }
+  SPP_TP_FLUSH();
+}
+
+// GEN: actor_trunk with fc1 handed to fc2 in registers
+template <class C, bool ACT, bool GEN>
+__device__ __forceinline__ void trunk_fwd_tiles(const SacArgs& p, const AcmScratch& z, float* smem, const float* tbl) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   float* big = smem + w * kLdsPerWave;
   float* small = big + kSmallRow * 32;
@@ -1481,8 +1600,8 @@ __global__ __launch_bounds__(256, 1) void k_sac_trunk_fwd(SacArgs p, AcmScratch 
     uint64_t a1lo = 0, a1hi = 0, a2lo = 0, a2hi = 0;
     SPP_TP(ACT ? 26 : 0);
     if constexpr (ACT) {
-      actor_trunk<C, true, C::NB_H2, 2 * C::AOUT, true>(p.actor, p.S, C::OB * L.ld4, L, p.AH1, p.AH2, a1lo, a1hi, a2lo,
-                                                        a2hi, p.ADH);
+      actor_trunk<C, true, C::NB_H2, 2 * C::AOUT, true, GEN>(p.actor, p.S, C::OB * L.ld4, L, p.AH1, p.AH2, a1lo, a1hi,
+                                                             a2lo, a2hi, p.ADH);
       uint64_t* mk = z.MASK + (int64_t)tile * 4 * 64 + lane;
       mk[0] = a1lo;
       mk[64] = a1hi;
@@ -1490,10 +1609,30 @@ __global__ __launch_bounds__(256, 1) void k_sac_trunk_fwd(SacArgs p, AcmScratch 
       mk[192] = a2hi;
       SPP_TP(27);  // actor trunk
     } else {
-      actor_trunk<C, false, C::NB_H2, 2 * C::AOUT, true>(p.actor, p.S2, C::OB * L.ld4, L, nullptr, nullptr, a1lo, a1hi,
-                                                         a2lo, a2hi, p.THD);
+      actor_trunk<C, false, C::NB_H2, 2 * C::AOUT, true, GEN>(p.actor, p.S2, C::OB * L.ld4, L, nullptr, nullptr, a1lo,
+                                                              a1hi, a2lo, a2hi, p.THD);
     }
   }
+}
+
+template <class C, bool ACT>
+__global__ __launch_bounds__(256, 1) void k_sac_trunk_fwd(SacArgs p, AcmScratch z) {
+  static_assert(C::NB_PAIR <= 2 && !C::BF, "narrow heads, fp32");
+  __shared__ float smem[kWavesPerWG * kLdsPerWave];
+  __shared__ __attribute__((aligned(16))) float tbl[kTabMax];
+  SPP_TP_INIT();
+  load_table(p, tbl);
+  trunk_fwd_tiles<C, ACT, false>(p, z, smem, tbl);
+  SPP_TP_FLUSH();
+}
+template <class C, bool ACT>
+__global__ __launch_bounds__(256, 1) void k_sac_trunk_fwd_gen(SacArgs p, AcmScratch z) {
+  static_assert(C::GEN_AFC1, "narrow heads, fp32, one observation block");
+  __shared__ float smem[kWavesPerWG * kLdsPerWave];
+  __shared__ __attribute__((aligned(16))) float tbl[kTabMax];
+  SPP_TP_INIT();
+  load_table(p, tbl);
+  trunk_fwd_tiles<C, ACT, true>(p, z, smem, tbl);
   SPP_TP_FLUSH();
 }
 

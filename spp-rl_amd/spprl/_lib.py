@@ -124,6 +124,7 @@ _SIGS = {
     "sppAgentGetTiming": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sppAgentStageSplit": (c_int, [c_void_p, P(c_int)]),
     "sppAgentCriticPairs": (c_int, [c_void_p, P(c_int)]),
+    "sppAgentActorGen": (c_int, [c_void_p, P(c_int)]),
     "sppAgentDwBigWaves": (c_int, [c_void_p, P(c_int)]),
     "sppAgentDwThin": (c_int, [c_void_p, P(c_int)]),
     "sppSynthEnvStep": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

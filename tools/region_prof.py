@@ -20,7 +20,7 @@ from spprl import _lib  # noqa: E402
 # T = k_sac_trunk_fwd, S = k_sac_squash_stage / k_sac_heads_stage (3 workgroups per CU: a slot's cycles are the
 # wave's own, while two other waves share its SIMD), R = the rest kernels (k_sac_critic_phase<C, true>,
 # k_sac_actor_phase<C, true, true>, k_sac_actor_trunk_bwd), whose "tile start" slots hold the hand-over read-backs.
-NAMES = {0: "tile start (R: + SCA / SLP read-back)", 1: "actor L1 (T)", 2: "actor L2 (T)", 3: "actor heads (T: -> THD)",
+NAMES = {0: "tile start (R: + SCA / SLP read-back)", 1: "actor L1 (T; SPP_ACTOR_GEN & 1: request only)", 2: "actor L2 (T; gen: + L1)", 3: "actor heads (T: -> THD)",
          4: "squash (S: + THD read-back)", 5: "ACM + target input (S: -> SCA / SLP)",
          6: "targ1 L1 (gen: request only)", 7: "targ1 L2 (gen: + L1)", 8: "targ2 L1 (gen: request only)",
          9: "targ2 L2 (gen: + L1)", 10: "y + critic input", 11: "critic L1 (gen: request only)",
@@ -35,7 +35,7 @@ NAMES = {0: "tile start (R: + SCA / SLP read-back)", 1: "actor L1 (T)", 2: "acto
          28: "A: squash (S: + ADH read-back)", 29: "A: ACM fwd (S: -> SCA / SLP)", 19: "A: q min",
          30: "A: critics L1 (fwd; gen: request only)",
          31: "A: critics L2 (fwd; gen: + L1) | DCA read-back (S)", 16: "A: ACM bwd (S)",
-         17: "A: heads bwd (S) | ADH read-back (R)", 18: "A: trunk bwd (R)"}
+         17: "A: heads bwd (S) | ADH read-back (R)", 18: "A: trunk bwd (R; SPP_ACTOR_GEN & 2: WhT under W2T)"}
 
 
 def main():
