@@ -74,7 +74,8 @@ sppStatus sppReplayDestroy(sppReplayHandle h);
 sppStatus sppReplayAddObs(sppReplayHandle h, const float* obs_dev /*[E][ob]*/, int E,
                           int64_t* slots_host_out /*[E]*/, void* stream);
 /* add_acm_action (:332-333) + add_timestep (:65-75) + addition (:133-137), E
- * transitions applied in env order (E = 1 is the reference exactly). */
+ * transitions applied in env order (E = 1 is the reference exactly).  A call
+ * refused for its arguments (a slot out of range at any env) changes nothing. */
 sppStatus sppReplayAddStep(sppReplayHandle h, const int64_t* prev_host, const int64_t* next_host, int E,
                            const float* act_dev /*[E][aout]*/, const float* acm_dev /*[E][ac]*/,
                            const float* rew_dev /*[E]*/, const uint8_t* done_dev /*[E]*/,

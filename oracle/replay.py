@@ -62,6 +62,18 @@ class OracleReplay:
             self.ts_idx += 1
         self.current_len = max(self.ts_idx, self.current_len)
 
+    # One vector step of E lockstep envs: the single-step methods above, applied in env order.
+    def add_obs_batch(self, rows):
+        return np.array([self.add_obs(r) for r in np.asarray(rows, np.float32).reshape(-1, self.ob)], np.int64)
+
+    def add_step_batch(self, prev, nxt, act, rew, done, end, acm=None):
+        E = len(prev)
+        act = np.asarray(act, np.float32).reshape(E, self.aout)
+        acm = np.zeros((E, self.ac), np.float32) if acm is None else np.asarray(acm, np.float32).reshape(E, self.ac)
+        for e in range(E):
+            self.add_acm_action(acm[e])
+            self.add_timestep(int(prev[e]), int(nxt[e]), act[e], rew[e], bool(done[e]), bool(end[e]))
+
     def gather(self, idx):
         o = self._obs[self._obs_idx[idx]].astype(np.float32)
         no = self._obs[self._next_obs_idx[idx]].astype(np.float32)

@@ -260,30 +260,37 @@ static sppStatus ring_reserve(sppReplayHandle h, int E) {
 sppStatus sppReplayAddStep(sppReplayHandle h, const int64_t* prev, const int64_t* next, int E, const float* act,
                            const float* acm, const float* rew, const uint8_t* done, const uint8_t* end, void* stream) {
   SPP_REQUIRE(h && prev && next && E > 0 && rew && done && end, SPP_E_INVALID_ARG, "add_step: bad args");
+  // A refused call leaves no trace: every env's slots are checked before anything changes, and the wrap rule
+  // runs on copies of the cursors that are stored (with the metadata slot and the generation) only once the
+  // whole batch has passed.
+  for (int e = 0; e < E; ++e)
+    SPP_REQUIRE(prev[e] >= 0 && prev[e] < h->d.cap && next[e] >= 0 && next[e] < h->d.cap, SPP_E_INVALID_ARG,
+                "add_step: slot out of range");
   sppStatus rs = ring_reserve(h, E);
   if (rs) return rs;
   const int slot = h->ring_pos;
-  h->ring_pos = (h->ring_pos + 1) % sppReplay::kRing;
-  ++h->gen;
   SPP_CHECK_HIP(hipEventSynchronize(h->ev[slot]));  // the copy that last used this slot is done
   int64_t* m = h->pinned[slot];
   // add_timestep wrap rule (replay_buffer.py:65-75) applied sequentially in env order
+  int64_t ts_idx = h->ts_idx, len = h->len;
   for (int e = 0; e < E; ++e) {
-    SPP_REQUIRE(prev[e] >= 0 && prev[e] < h->d.cap && next[e] >= 0 && next[e] < h->d.cap, SPP_E_INVALID_ARG,
-                "add_step: slot out of range");
     m[e] = prev[e];
     m[E + e] = next[e];
-    m[2 * E + e] = h->ts_idx;
-    if (next[e] < h->ts_idx) {
-      h->len = h->ts_idx + 1;
-      h->ts_idx = 0;
+    m[2 * E + e] = ts_idx;
+    if (next[e] < ts_idx) {
+      len = ts_idx + 1;
+      ts_idx = 0;
     } else {
-      h->ts_idx += 1;
+      ts_idx += 1;
     }
-    h->len = std::max(h->ts_idx, h->len);
-    SPP_REQUIRE(h->ts_idx <= h->d.cap, SPP_E_STATE, "add_step: ts ring overflow (obs ring too small)");
-    if (h->ts_idx == h->d.cap) h->ts_idx = h->d.cap - 1;  // unreachable with the reference wrap rule
+    len = std::max(ts_idx, len);
+    SPP_REQUIRE(ts_idx <= h->d.cap, SPP_E_STATE, "add_step: ts ring overflow (obs ring too small)");
+    if (ts_idx == h->d.cap) ts_idx = h->d.cap - 1;  // unreachable with the reference wrap rule
   }
+  h->ts_idx = ts_idx;
+  h->len = len;
+  h->ring_pos = (slot + 1) % sppReplay::kRing;
+  ++h->gen;
   SPP_CHECK_HIP(hipMemcpyAsync(h->dev_meta[slot], m, sizeof(int64_t) * 3 * E, hipMemcpyHostToDevice, S(stream)));
   SPP_CHECK_HIP(hipEventRecord(h->ev[slot], S(stream)));
   const int64_t n_el = (int64_t)E * (h->d.aout + h->d.ac + 1);
