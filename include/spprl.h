@@ -100,6 +100,19 @@ sppStatus sppReplayObsStats(sppReplayHandle h, float* mean, float* std, float* m
  * workgroup candidate-list capacity to list_cap and the per-(column, target) overflow list to ovf_cap keys (0:
  * the full capacities), so the overflow fallbacks run at small sizes.  Results stay exact at any capacity. */
 sppStatus sppReplaySetObsStatsCaps(sppReplayHandle h, int list_cap, int ovf_cap);
+/* sppReplayObsStats beside the work already queued on its caller's stream (environment SPP_STATS_OVERLAP = 1 / 0,
+ * read when the handle is made; sppReplayStatsOverlap reports it).  The statistics kernels then run on a
+ * least-priority stream of the handle's, ordered behind the last AddObs / AddStep, into a library-owned copy of
+ * the four vectors, and a small copy on the caller's stream publishes them: the contract above is unchanged
+ * (work queued on `stream` after the call sees the new values, work queued before it the old ones).  The copy
+ * also carries the running max / min, so a caller that writes the four arrays itself (a checkpoint restore)
+ * says so with sppReplayObsStatsInvalidate.  The call runs on the caller's stream, as with SPP_STATS_OVERLAP=0,
+ * whenever the library cannot prove the two equal: the first call on a handle, first_update != 0, other array
+ * pointers than the last call's, after Invalidate, and after GetView until the next AddObs / AddStep / Reset.
+ * sppReplayStatsOverlapCounts: the calls that took each path so far (calls skipped at len <= 10 count as neither). */
+sppStatus sppReplayObsStatsInvalidate(sppReplayHandle h);
+int sppReplayStatsOverlap(sppReplayHandle h);
+sppStatus sppReplayStatsOverlapCounts(sppReplayHandle h, uint64_t* overlapped, uint64_t* serial);
 /* Data-parallel update_obs_mean_std over the union of the ranks' replay shards
  * (SURVEY.md §8e): exact global mean / std (fp64 sums about a replicated pivot,
  * e.g. the current obs_mean) and exact global 99th / 1st percentiles (radix select

@@ -92,6 +92,10 @@ struct sppMT19937 {
 using namespace spp;
 
 // ================================================================== replay handle
+// sppReplayObsStats on a side stream beside the update's kernels (SPP_STATS_OVERLAP overrides, read when the
+// handle is made).  On: faster on MI355X by the project's bench rule.
+constexpr int kStatsOverlapDefault = 1;
+
 struct sppReplay {
   ReplayDev d{};
   int device = 0, num_cu = 256;
@@ -122,6 +126,23 @@ struct sppReplay {
   int st_cap_lim = 0, st_ovf_lim = 0;  // sppReplaySetObsStatsCaps (0: the full capacities)
   void* dp_q = nullptr;  // one-pass data-parallel statistics: per (column, target, rank) query state
   uint32_t* dp_cand = nullptr;  // and the compacted local candidates + counts
+  // Side stream of sppReplayObsStats (SPP_STATS_OVERLAP): the statistics kernels run on `side`
+  // (least priority, non-blocking) beside whatever the caller's stream still holds, and write `shadow`
+  // [mean | std | max | min][ob]; k_st_publish copies it to the caller's arrays on the caller's stream.
+  //   ev_rows     recorded on the writer's stream after the last ring write (AddObs / AddStep): side waits on it
+  //   ev_done     recorded on side after each call's kernels: the publish, later ring writers and every other
+  //               user of the sf_* scratch wait on it
+  //   ev_scratch  recorded on a caller's stream after it used the sf_* scratch or refreshed the shadow itself
+  //               (the serial path, the data-parallel paths): side waits on it once
+  int overlap = 0;
+  hipStream_t side = nullptr;
+  hipEvent_t ev_rows = nullptr, ev_done = nullptr, ev_scratch = nullptr;
+  bool rows_rec = false, done_rec = false, scratch_rec = false;
+  float* shadow = nullptr;
+  bool shadow_valid = false;  // shadow == the caller's arrays as of the last call (else: the serial path)
+  bool view_open = false;     // gen was last bumped by GetView: the caller may write the rows at any time
+  const float* last_out[4] = {};
+  uint64_t n_overlapped = 0, n_serial = 0;
 };
 
 extern "C" {
@@ -205,14 +226,64 @@ sppStatus sppReplayCreate(sppReplayHandle* out, int64_t cap, int ob, int aout, i
     return SPP_E_OOM;
   }
   for (int i = 0; i < sppReplay::kRing; ++i) SPP_CHECK_HIP(hipEventCreateWithFlags(&h->ev[i], hipEventDisableTiming));
+  {
+    const char* e = getenv("SPP_STATS_OVERLAP");
+    h->overlap = (e && *e) ? (atoi(e) != 0) : kStatsOverlapDefault;
+  }
   *out = h;
+  return SPP_OK;
+}
+
+// ---- side stream of the obs statistics (the fields' comment in sppReplay)
+static sppStatus side_ensure(sppReplayHandle h) {
+  if (h->side) return SPP_OK;
+  int cur = 0;
+  SPP_CHECK_HIP(hipGetDevice(&cur));
+  if (cur != h->device) SPP_CHECK_HIP(hipSetDevice(h->device));
+  int least = 0, greatest = 0;
+  hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+  // non-blocking: the caller's stream may be the null stream, which a blocking stream would wait for
+  e = e ? e : hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, least);
+  e = e ? e : hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming);
+  e = e ? e : hipEventCreateWithFlags(&h->ev_scratch, hipEventDisableTiming);
+  e = e ? e : hipMalloc(&h->shadow, sizeof(float) * 4 * h->d.ob);
+  if (cur != h->device) hipSetDevice(cur);
+  SPP_CHECK_HIP(e);
+  return SPP_OK;
+}
+// before a ring write, or a use of the sf_* scratch, on stream st: the side stream's last statistics call is done
+static sppStatus side_wait_done(sppReplayHandle h, hipStream_t st) {
+  if (h->done_rec) SPP_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done, 0));
+  return SPP_OK;
+}
+// after the last ring write of an entry point on stream st
+static sppStatus side_rows_written(sppReplayHandle h, hipStream_t st) {
+  h->view_open = false;
+  if (!h->overlap) return SPP_OK;
+  if (!h->ev_rows) SPP_CHECK_HIP(hipEventCreateWithFlags(&h->ev_rows, hipEventDisableTiming));
+  SPP_CHECK_HIP(hipEventRecord(h->ev_rows, st));
+  h->rows_rec = true;
+  return SPP_OK;
+}
+// after stream st used the sf_* scratch (and perhaps wrote the caller's statistics arrays) itself
+static sppStatus side_scratch_used(sppReplayHandle h, hipStream_t st, bool shadow_stale) {
+  if (shadow_stale) h->shadow_valid = false;
+  if (!h->side) return SPP_OK;
+  SPP_CHECK_HIP(hipEventRecord(h->ev_scratch, st));
+  h->scratch_rec = true;
   return SPP_OK;
 }
 
 sppStatus sppReplayDestroy(sppReplayHandle h) {
   if (!h) return SPP_OK;
   hipSetDevice(h->device);
+  if (h->side) hipStreamSynchronize(h->side);
   hipDeviceSynchronize();
+  if (h->side) hipStreamDestroy(h->side);
+  if (h->ev_rows) hipEventDestroy(h->ev_rows);
+  if (h->ev_done) hipEventDestroy(h->ev_done);
+  if (h->ev_scratch) hipEventDestroy(h->ev_scratch);
+  hipFree(h->shadow);
   ReplayDev& d = h->d;
   hipFree(d.obs); hipFree(d.obs_idx); hipFree(d.rec); hipFree((void*)d.acm_cols);
   for (int i = 0; i < sppReplay::kRing; ++i) {
@@ -231,9 +302,13 @@ sppStatus sppReplayAddObs(sppReplayHandle h, const float* obs, int E, int64_t* s
   SPP_REQUIRE(h && obs && E > 0 && E <= h->d.cap, SPP_E_INVALID_ARG, "add_obs: bad args");
   const int64_t base = h->obs_idx;
   ++h->gen;
+  sppStatus sw = side_wait_done(h, S(stream));  // a statistics call on the side stream may still read the rows
+  if (sw) return sw;
   hipLaunchKernelGGL(k_replay_add_obs, dim3(cdiv((int64_t)E * h->d.ob, 256)), dim3(256), 0, S(stream), h->d.obs,
                      h->d.cap, h->d.ob, obs, E, base);
   SPP_CHECK_HIP(hipGetLastError());
+  sw = side_rows_written(h, S(stream));
+  if (sw) return sw;
   for (int e = 0; e < E; ++e) {
     if (slots) slots[e] = (base + e) % h->d.cap;
   }
@@ -293,11 +368,13 @@ sppStatus sppReplayAddStep(sppReplayHandle h, const int64_t* prev, const int64_t
   ++h->gen;
   SPP_CHECK_HIP(hipMemcpyAsync(h->dev_meta[slot], m, sizeof(int64_t) * 3 * E, hipMemcpyHostToDevice, S(stream)));
   SPP_CHECK_HIP(hipEventRecord(h->ev[slot], S(stream)));
+  sppStatus sw = side_wait_done(h, S(stream));  // k_st_pass on the side stream reads obs_idx
+  if (sw) return sw;
   const int64_t n_el = (int64_t)E * (h->d.aout + h->d.ac + 1);
   hipLaunchKernelGGL(k_replay_add_step, dim3(cdiv(n_el, 256)), dim3(256), 0, S(stream), h->d, h->dev_meta[slot], E,
                      act, acm, rew, done, end);
   SPP_CHECK_HIP(hipGetLastError());
-  return SPP_OK;
+  return side_rows_written(h, S(stream));
 }
 
 sppStatus sppReplayState(sppReplayHandle h, int64_t* obs_idx, int64_t* ts_idx, int64_t* len) {
@@ -310,7 +387,8 @@ sppStatus sppReplayState(sppReplayHandle h, int64_t* obs_idx, int64_t* ts_idx, i
 sppStatus sppReplayReset(sppReplayHandle h) {
   SPP_REQUIRE(h, SPP_E_INVALID_ARG, "null handle");
   h->obs_idx = h->ts_idx = h->len = 0;
-  ++h->gen;
+  ++h->gen;  // (no device write: the last rows event still covers every row)
+  h->view_open = false;
   return SPP_OK;
 }
 
@@ -326,6 +404,10 @@ sppStatus sppReplayGather(sppReplayHandle h, const int64_t* idx, int B, float* o
 sppStatus sppReplayGetView(sppReplayHandle h, sppReplayView* v) {
   SPP_REQUIRE(h && v, SPP_E_INVALID_ARG, "null");
   ++h->gen;  // the caller may write the ring through the view
+  // ... on any stream and at any time from now on, unseen by the library: the side stream drains here, and
+  // sppReplayObsStats stays on its caller's stream until AddObs / AddStep / Reset write through the library again
+  if (h->side) SPP_CHECK_HIP(hipStreamSynchronize(h->side));
+  h->view_open = true;
   v->obs = h->d.obs;
   v->obs_idx = h->d.obs_idx;
   v->rec = h->d.rec;
@@ -459,6 +541,7 @@ static int st_ovf_cap(sppReplayHandle h) {
 
 sppStatus sppReplaySetObsStatsCaps(sppReplayHandle h, int list_cap, int ovf_cap) {
   SPP_REQUIRE(h && list_cap >= 0 && ovf_cap >= 0, SPP_E_INVALID_ARG, "set_obs_stats_caps: bad args");
+  if (h->side) SPP_CHECK_HIP(hipStreamSynchronize(h->side));  // (a test hook: no statistics call in flight across it)
   h->st_cap_lim = list_cap;
   h->st_ovf_lim = ovf_cap;
   return SPP_OK;
@@ -479,6 +562,9 @@ static sppStatus stats_fast_alloc(sppReplayHandle h) {
   return SPP_OK;
 }
 
+static sppStatus stats_chain(sppReplayHandle h, int64_t len, int nblk, float* mean, float* std, float* max_obs,
+                             float* min_obs, int first_update, hipStream_t st);
+
 sppStatus sppReplayObsStats(sppReplayHandle h, float* mean, float* std, float* max_obs, float* min_obs,
                             int first_update, void* stream) {
   SPP_REQUIRE(h && mean && std && max_obs && min_obs, SPP_E_INVALID_ARG, "obs_stats: bad args");
@@ -493,6 +579,70 @@ sppStatus sppReplayObsStats(sppReplayHandle h, float* mean, float* std, float* m
   sppStatus s = stats_fast_alloc(h);
   if (s) return s;
   hipStream_t st = S(stream);
+  float* const out[4] = {mean, std, max_obs, min_obs};
+  if (!h->overlap) {
+    ++h->n_serial;
+    return stats_chain(h, len, nblk, mean, std, max_obs, min_obs, first_update, st);
+  }
+  s = side_ensure(h);
+  if (s) return s;
+  // The side stream is taken only when the library can prove that the shadow holds what the caller's arrays
+  // will hold once the caller's stream reaches this point, and that it sees every write of the rows.
+  bool same = true;
+  for (int i = 0; i < 4; ++i) same = same && h->last_out[i] == out[i];
+  const bool side_ok = h->shadow_valid && same && !first_update && !h->view_open && h->rows_rec;
+  for (int i = 0; i < 4; ++i) h->last_out[i] = out[i];
+  float* const sh[4] = {h->shadow, h->shadow + ob, h->shadow + 2 * ob, h->shadow + 3 * ob};
+  if (!side_ok) {  // today's code on the caller's stream, then shadow <- the caller's arrays
+    s = side_wait_done(h, st);  // the scratch is shared with the side stream's calls
+    if (s) return s;
+    s = stats_chain(h, len, nblk, mean, std, max_obs, min_obs, first_update, st);
+    if (s) return s;
+    const StPublishArgs ra{{sh[0], sh[1], sh[2], sh[3]}, {mean, std, max_obs, min_obs}, ob};
+    hipLaunchKernelGGL(k_st_publish, dim3(4), dim3(128), 0, st, ra);
+    SPP_CHECK_HIP(hipGetLastError());
+    s = side_scratch_used(h, st, false);
+    if (s) return s;
+    h->shadow_valid = true;
+    ++h->n_serial;
+    return SPP_OK;
+  }
+  // Never a wait on anything recorded on st now: the update queued ahead of this call is what the kernels run
+  // beside.  ev_rows was recorded behind the last ring write, ev_scratch behind the last serial use of the scratch.
+  SPP_CHECK_HIP(hipStreamWaitEvent(h->side, h->ev_rows, 0));
+  if (h->scratch_rec) {
+    SPP_CHECK_HIP(hipStreamWaitEvent(h->side, h->ev_scratch, 0));
+    h->scratch_rec = false;  // the side stream's own order covers it from here on
+  }
+  s = stats_chain(h, len, nblk, sh[0], sh[1], sh[2], sh[3], 0, h->side);
+  if (s) return s;
+  SPP_CHECK_HIP(hipEventRecord(h->ev_done, h->side));
+  h->done_rec = true;
+  SPP_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done, 0));  // this call's chain only: a later record does not move it
+  const StPublishArgs pa{{mean, std, max_obs, min_obs}, {sh[0], sh[1], sh[2], sh[3]}, ob};
+  hipLaunchKernelGGL(k_st_publish, dim3(4), dim3(128), 0, st, pa);
+  SPP_CHECK_HIP(hipGetLastError());
+  ++h->n_overlapped;
+  return SPP_OK;
+}
+
+sppStatus sppReplayObsStatsInvalidate(sppReplayHandle h) {
+  SPP_REQUIRE(h, SPP_E_INVALID_ARG, "null handle");
+  h->shadow_valid = false;
+  return SPP_OK;
+}
+int sppReplayStatsOverlap(sppReplayHandle h) { return h ? h->overlap : -1; }
+sppStatus sppReplayStatsOverlapCounts(sppReplayHandle h, uint64_t* overlapped, uint64_t* serial) {
+  SPP_REQUIRE(h, SPP_E_INVALID_ARG, "null handle");
+  if (overlapped) *overlapped = h->n_overlapped;
+  if (serial) *serial = h->n_serial;
+  return SPP_OK;
+}
+
+// The statistics kernels of one call on stream st, outputs to the given arrays (the caller's, or the shadow).
+static sppStatus stats_chain(sppReplayHandle h, int64_t len, int nblk, float* mean, float* std, float* max_obs,
+                             float* min_obs, int first_update, hipStream_t st) {
+  const int ob = h->d.ob;
   const bool big = len > kStBigLen;
   const int ns = (int)std::min<int64_t>(len, big ? kStSampBig : kStSampSmall);
   if (h->sf_gen != h->gen || h->sf_len != len) {  // else: the same rows' bracket is in sf_bounds
@@ -552,6 +702,8 @@ sppStatus sppReplayObsStatsDP1(sppReplayHandle h, int phase, int world, int rank
   const int Sl = sppReplayObsStatsDP1SampleRows(h, world, n_global);
   uint32_t* mine = samp + (int64_t)rank * ob * Sl;
   const int cap = st_cap(h), ovf_cap = st_ovf_cap(h);
+  s = side_wait_done(h, st);  // the sf_* scratch is shared with sppReplayObsStats' side stream
+  if (s) return s;
   StDpArgs da{h->d, len, n_global, nblk, cap, ovf_cap, h->sf_bounds, h->sf_wgl, h->sf_wgn, h->sf_ovf, h->sf_ovf_n,
               h->dp_cand, dp_ncand, exch, hist, (DpQuery*)h->dp_q, pivot, mean, std, max_obs, min_obs, first_update};
   if (phase == 0) {
@@ -585,7 +737,7 @@ sppStatus sppReplayObsStatsDP1(sppReplayHandle h, int phase, int world, int rank
     hipLaunchKernelGGL(k_dp_final, dim3(ob, 2), dim3(128), 0, st, da);
   }
   SPP_CHECK_HIP(hipGetLastError());
-  return SPP_OK;
+  return side_scratch_used(h, st, true);  // (phase 6 writes the caller's arrays: the shadow is stale)
 }
 
 int sppReplayObsStatsDPHistSize(sppReplayHandle h) {
@@ -607,6 +759,11 @@ sppStatus sppReplayObsStatsDP(sppReplayHandle h, int step, const float* pivot, d
   sppStatus s = stats_alloc(h);
   if (s) return s;
   hipStream_t st = S(stream);
+  // (its scratch is st_*, its own; it writes the caller's arrays, so the side stream's shadow goes stale and
+  // the caller's stream first passes every publish still queued)
+  s = side_wait_done(h, st);
+  if (s) return s;
+  h->shadow_valid = false;
   const int npass = stats_npass(h);
   SPP_REQUIRE(step <= npass + 1, SPP_E_INVALID_ARG, "obs_stats_dp: step %d > %d", step, npass + 1);
   *done = 0;

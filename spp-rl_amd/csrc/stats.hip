@@ -670,6 +670,20 @@ __global__ __launch_bounds__(kStSelThreads) void k_st_select(StSelArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- publish
+// sppReplayObsStats on its side stream (api.hip) writes a library-owned shadow of the four output vectors;
+// this copy, on the caller's stream behind the side stream's done event, makes them the caller's.  Also the
+// other way round (shadow <- the caller's arrays) after a call that ran on the caller's stream.  Grid 4 x 128.
+struct StPublishArgs {
+  float* dst[4];
+  const float* src[4];
+  int ob;
+};
+__global__ __launch_bounds__(128) void k_st_publish(StPublishArgs a) {
+  const int c = threadIdx.x;
+  if (c < a.ob) a.dst[blockIdx.x][c] = a.src[blockIdx.x][c];
+}
+
 // ================================================================ data-parallel: one data pass
 // update_obs_mean_std over the union of the ranks' shards (replay_buffer.py:83-96) with ONE
 // read of the local rows per call (the host runs the collectives between the phases):

@@ -170,6 +170,9 @@ _SIGS = {
                                     c_void_p, c_void_p, c_int, P(c_int), c_void_p]),
     "sppReplayObsStatsDP1SampleRows": (c_int, [c_void_p, c_int, c_int64]),
     "sppReplaySetObsStatsCaps": (c_int, [c_void_p, c_int, c_int]),
+    "sppReplayObsStatsInvalidate": (c_int, [c_void_p]),
+    "sppReplayStatsOverlap": (c_int, [c_void_p]),
+    "sppReplayStatsOverlapCounts": (c_int, [c_void_p, P(c_uint64), P(c_uint64)]),
     "sppReplayObsStatsDP1": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "sppObsNormalize": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

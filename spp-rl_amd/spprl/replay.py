@@ -272,6 +272,7 @@ class BufferAcMOffPolicy:
             n_global = self._ng
         if n_global <= 10:  # replay_buffer.py:84, on the global buffer
             return
+        call("sppReplayObsStatsInvalidate", self._h)  # the data-parallel kernels write the four vectors themselves
         if allgather is not None:
             return self._obs_stats_dp1(allreduce_sum, allgather, n_global)
         if getattr(self, "_dp_hist", None) is None:
@@ -358,6 +359,7 @@ class BufferAcMOffPolicy:
 
     def load_normalizer_state(self, d):
         """rl.py:276-279: mean and std always; the min-max pair only when the checkpoint holds both."""
+        call("sppReplayObsStatsInvalidate", self._h)  # the library's copy of the four vectors is stale from here
         self.obs_mean.copy_(torch.as_tensor(d["obs_mean"]))
         self.obs_std.copy_(torch.as_tensor(d["obs_std"]))
         if d.get("min_obs") is not None and d.get("max_obs") is not None:
