@@ -1,10 +1,11 @@
 """Build libspprl.so (gfx950) in-tree with hipcc.  Usage: python spp-rl_amd/build.py [--force]
 
-The library is two C-ABI units (csrc/api.hip, and csrc/api_onp.hip with the on-policy handle and its non-template
-kernels) plus one unit per phase-kernel config family (csrc/ks_*.hip); they compile in parallel into build/ and
-link into spp-rl_amd/spprl/libspprl.so.  Every compile writes a depfile (build/<unit>.o.d): a unit is recompiled
-when its object is older than any file the compiler read for it.  --prof builds api.hip, which then includes
-api_onp.hip and the kernel sets, as one unit into libspprl_prof.so.
+The library is four C-ABI units (csrc/api.hip with the off-policy agent handle, csrc/api_comm.hip with the RCCL
+exchange, csrc/api_onp.hip with the on-policy handle, csrc/api_replay.hip with the replay ring and its statistics;
+each with its own non-template kernels) plus one unit per phase-kernel config family (csrc/ks_*.hip); they compile
+in parallel into build/ and link into spp-rl_amd/spprl/libspprl.so.  Every compile writes a depfile
+(build/<unit>.o.d): a unit is recompiled when its object is older than any file the compiler read for it.  --prof
+builds api.hip, which then includes the other three api units and the kernel sets, as one unit into libspprl_prof.so.
 """
 import glob
 import os
@@ -26,7 +27,7 @@ def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*"))) + [os.path.join(REPO, "include", "spprl.h")]
 
 
-API_UNITS = ("api.hip", "api_onp.hip")  # by name: no other api*.hip file is ever compiled or linked
+API_UNITS = ("api.hip", "api_comm.hip", "api_onp.hip", "api_replay.hip")  # by name: no other api*.hip file is ever compiled or linked
 
 
 def units():

@@ -1,6 +1,6 @@
 // libspprl C-ABI, the on-policy unit: the on-policy handle (A2C / PPO nets) with its persistent epoch / critic
 // launches, and the free-standing on-policy stream utilities (GAE, clip loss, advantage norms).  Compiles ppo.hip, the
-// onp*.hip kernels and the PPO actor / critic (HEAD 1 / 2) instantiations of k_mlp_sgd; everything else is api.hip's.
+// onp*.hip kernels and the PPO actor / critic (HEAD 1 / 2) instantiations of k_mlp_sgd; the off-policy agent is api.hip's.
 #include <algorithm>
 #include <memory>
 #include <vector>

@@ -1,11 +1,12 @@
-// Host side of the C-ABI that both api.hip and api_onp.hip use: the stream cast, the device-array, job-set and
-// pack-plan types, and the helpers and kernel launches that api.hip defines and api_onp.hip calls.  Host only
+// Host side of the C-ABI that the two handle units with networks, api.hip and api_onp.hip, use: the job-set and
+// pack-plan types, and the helpers and kernel launches that api.hip defines and api_onp.hip calls, on top of
+// host_base.h (the stream cast, the device-array type, the calls into api_replay.hip / api_comm.hip).  Host only
 // (device code does not need it).
 #pragma once
 #include <algorithm>
 #include <vector>
 
-#include "../../include/spprl.h"
+#include "host_base.h"
 #include "internal.h"
 #include "layout.h"
 #include "sac_kernels.h"
@@ -14,25 +15,9 @@
 
 namespace spp {
 
-static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 struct NetBufs {
   float *p = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;
   int64_t n = 0;
-};
-
-template <typename T>
-struct DevArray {
-  T* ptr = nullptr;
-  size_t n = 0;
-  hipError_t alloc(size_t count) {
-    n = count;
-    return hipMalloc(&ptr, sizeof(T) * std::max<size_t>(count, 1));
-  }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-  }
 };
 
 // A weight-gradient job set (dw.hip): up to two phases launched separately.

@@ -1,6 +1,6 @@
 // Kernel-set table: dims -> phase-kernel instantiations.  Each config family is
 // instantiated in its own translation unit (ks_*.hip) so the library builds in
-// parallel; api.hip only holds the function pointers.
+// parallel; api.hip, the agent's unit and the only api unit to include this, only holds the function pointers.
 #pragma once
 #include "sac.hip"
 #include "sac_bf.h"

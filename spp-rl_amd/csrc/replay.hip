@@ -699,23 +699,4 @@ __global__ void k_obs_normalize(const float* __restrict__ x, int64_t n, int ob, 
   out[i] = obs_norm1(x[i], (int)(i % ob), lo, hi, mean, std, min_max, inverse);
 }
 
-// The staged batch's sample_batch tail (replay_buffer.py:247-249) and DDPG_AcM.make_unbiased_update
-// (acm/off_policy/ddpg_acm.py:59-73) on the feature-major staging arrays [ob][Bp]: with `norm`, the staged
-// obs and next obs are normalised in place (the buffer's obs_norm); with `act_next`, the critic's action
-// operand becomes the (normalised) next obs.  Columns b >= B (padding) stay zero.
-__global__ void k_stage_post(float* S, float* S2, float* ACT, int ob, int B, int Bp, const float* lo, const float* hi,
-                             const float* mean, const float* std, int min_max, int norm, int act_next) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)ob * B) return;
-  const int f = (int)(i / B), b = (int)(i - (int64_t)f * B);
-  const int64_t o = (int64_t)f * Bp + b;
-  float s2 = S2[o];
-  if (norm) {
-    S[o] = obs_norm1(S[o], f, lo, hi, mean, std, min_max, 0);
-    s2 = obs_norm1(s2, f, lo, hi, mean, std, min_max, 0);
-    S2[o] = s2;
-  }
-  if (act_next) ACT[o] = s2;
-}
-
 }  // namespace spp

@@ -671,7 +671,7 @@ __global__ __launch_bounds__(kStSelThreads) void k_st_select(StSelArgs a) {
 }
 
 // ---------------------------------------------------------------- publish
-// sppReplayObsStats on its side stream (api.hip) writes a library-owned shadow of the four output vectors;
+// sppReplayObsStats on its side stream (api_replay.hip) writes a library-owned shadow of the four output vectors;
 // this copy, on the caller's stream behind the side stream's done event, makes them the caller's.  Also the
 // other way round (shadow <- the caller's arrays) after a call that ran on the caller's stream.  Grid 4 x 128.
 struct StPublishArgs {

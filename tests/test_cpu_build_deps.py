@@ -105,13 +105,35 @@ def test_units_are_the_api_units_and_every_kernel_set(tmp_path, monkeypatch):
     real = os.path.join(REPO, "spp-rl_amd", "csrc")
     got = [os.path.relpath(u, real) for u in B.units()]
     ks = sorted(os.path.basename(f) for f in glob.glob(os.path.join(real, "ks_*.hip")))
-    assert ks and got == ["api.hip", "api_onp.hip"] + ks
+    api = ["api.hip", "api_comm.hip", "api_onp.hip", "api_replay.hip"]
+    assert ks and got == api + ks
     assert all(os.path.exists(u) for u in B.units())
     # no other file is picked up, whatever it is called
-    for f in ("api.hip", "api_onp.hip", "api_old.hip", "api.hip.bak", "unity_prof.hip", "ks_x.hip", "ks_x.hip.orig", "dw.hip"):
+    for f in api + ["api_old.hip", "api.hip.bak", "unity_prof.hip", "ks_x.hip", "ks_x.hip.orig", "dw.hip"]:
         (tmp_path / f).write_text("")
     monkeypatch.setattr(B, "CSRC", str(tmp_path))
-    assert [os.path.basename(u) for u in B.units()] == ["api.hip", "api_onp.hip", "ks_x.hip"]
+    assert [os.path.basename(u) for u in B.units()] == api + ["ks_x.hip"]
+
+
+def test_api_units_keep_to_their_own_kernel_files():
+    """The real depfiles of the last build: the replay unit alone compiles replay.hip / stats.hip and reads nothing
+    of the agent's; the RCCL unit reads no kernel file at all."""
+    obj = os.path.join(REPO, "spp-rl_amd", "build")
+    if not glob.glob(os.path.join(obj, "*.o.d")):
+        pytest.skip("no depfiles under spp-rl_amd/build (run __graft_entry__.build())")
+
+    def names(unit):
+        with open(os.path.join(obj, unit + ".o.d")) as f:
+            deps = B.parse_depfile(f.read())
+        assert deps, unit
+        return {os.path.basename(d) for d in deps}
+
+    replay = names("api_replay")
+    assert {"replay.hip", "stats.hip"} <= replay
+    assert not replay & {"sac.hip", "ddpg.hip", "kset.h", "sgd_mlp.hip"}
+    assert not names("api") & {"replay.hip", "stats.hip"}
+    assert [d for d in names("api_comm") if d.endswith(".hip")] == ["api_comm.hip"]
+    assert not names("api_onp") & {"replay.hip", "stats.hip"}
 
 
 def test_job_count_comes_from_the_environment_and_is_capped(monkeypatch):

@@ -1,4 +1,4 @@
-"""sppReplayObsStats on its side stream (SPP_STATS_OVERLAP=1, csrc/api.hip) against the same
+"""sppReplayObsStats on its side stream (SPP_STATS_OVERLAP=1, csrc/api_replay.hip) against the same
 calls on the caller's stream (SPP_STATS_OVERLAP=0) and against numpy on the same rows the way tests/test_gpu_stats.py
 compares: percentiles bit-exact, mean / std within fp32 rounding of the fp64 result (rtol 2e-7), running max / min.
 The two modes must agree bit for bit after every call, the outputs must change at the call's place in the caller's
